@@ -51,5 +51,6 @@ inline float* fptr_mut(at::Tensor& t) { return (t.defined() && t.numel()) ? t.da
 void bind_loss(pybind11::module_& m);
 void bind_optim(pybind11::module_& m);
 void bind_raster(pybind11::module_& m);
+void bind_metrics(pybind11::module_& m);
 
 }  // namespace b3

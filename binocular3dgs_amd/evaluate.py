@@ -1,0 +1,222 @@
+"""Held-out view evaluation: batched renders and on-device metrics.
+
+The reference does two things with a trained scene besides training it:
+
+    train.py:226-261      training_report   test views + 5 train views at --test_iterations: mean L1 and PSNR
+    render.py:24-49 +     renders to PNG, then SSIM / PSNR / LPIPS per view (DTU object masks), results.json +
+    metrics.py:37-124     per_view.json
+
+Here both run on the device without a round trip through files:
+  * render_views() renders up to 8 views per b3gs_forward_raw_batch launch through a FusedRasterizer that evaluation owns
+    (its own slots, binning buffers, overflow / high-water words and open-tile prediction: the training rasterizer is never
+    touched), without gradients, one-round binning and the full 32-bit depth sort;
+  * the metric sums of every view of a launch come from ONE b3gs_image_metrics_batch (csrc/metrics.hip: clamp or 8-bit
+    round trip, mask composite, fp64 sums, fixed-order fold), the SSIM of all of them from one b3gs_ssim_forward.
+The host reads the device once per render batch (the overflow word) and once at the end (the sums).
+
+Two numbers that are easy to confuse:
+  * training_report's PSNR (mode "report") is image_utils.psnr on a 3-D [3,H,W] tensor: the MEAN OF THE THREE
+    PER-CHANNEL PSNRs, of images clamped to [0,1];
+  * metrics.py's PSNR (mode "png") takes the masked branch of image_utils.psnr: one MSE over every element whose mask is
+    exactly 1, of images that went through the 8-bit PNG round trip and the mask composite.  An empty mask gives NaN,
+    identical images +inf (as in the reference).
+LPIPS is not reproduced: its VGG weights are a network download.
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+from typing import Callable, Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+MAX_BATCH = 8          # views per forward launch (B3GS_MAX_FUSED_VIEWS)
+CLAMP, QUANTIZE = 1, 2  # B3GS_METRIC_CLAMP / B3GS_METRIC_QUANTIZE of include/b3gs_raster.h
+MODES = {"report": CLAMP, "png": QUANTIZE}
+
+
+# ---- batched renders ---------------------------------------------------------------------------------------------------
+def _renderer(model, W: int, H: int, first_views: Sequence, bg: torch.Tensor, batch: int, capacity: Optional[int]):
+    """The evaluation-owned FusedRasterizer of (model, W, H): cached on the model, rebuilt when P changed (densification)."""
+    from .fused import FusedRasterizer
+    cache = model.__dict__.setdefault("_b3gs_eval_renderers", {})
+    fr = cache.get((W, H))
+    if fr is None or fr.P != model.get_xyz.shape[0] or len(fr.slots) < batch or capacity is not None:
+        fr = FusedRasterizer(model, W, H, num_slots=batch, binning_capacity=capacity, want_means2D=False,
+                             schedule="batched", seg1_fraction=0.0)
+        if capacity is None:
+            fr.fit_capacity([(c, k) for k, c in enumerate(first_views[:batch])], bg)
+        cache[(W, H)] = fr
+    return fr
+
+
+def _render_checked(fr, cams: Sequence, bg: torch.Tensor) -> List[dict]:
+    """One launch for `cams`; one read of the overflow word; grow + render again when a tile list did not fit."""
+    views = [(c, k) for k, c in enumerate(cams)]
+    for _ in range(3):
+        outs = fr.render_batch(views, bg)
+        flag = int(fr.overflow_flag.item())
+        if flag:
+            fr.overflow_flag.zero_()
+        if flag & 8:
+            from ._lib import B3gsError
+            raise B3gsError("a view was rendered from the depth order of the camera it names as `same_depth_as`, but their "
+                            "depth keys differ")
+        if not flag & 1:
+            return outs
+        fr.grow(need=int(fr.high_water.max().item()))
+    raise RuntimeError("evaluation render: the binning capacity still overflowed after growing twice")
+
+
+def _batches(model, cameras: Sequence, bg: torch.Tensor, batch: int, capacity: Optional[int] = None):
+    """Yields (indices into `cameras`, [3,H,W] images) per launch, views of one W x H together.  The images are the
+    renderer's slot buffers: valid until the next item is drawn."""
+    batch = max(1, min(int(batch), MAX_BATCH))
+    groups: Dict[tuple, List[int]] = {}
+    for i, cam in enumerate(cameras):
+        groups.setdefault((int(cam.image_width), int(cam.image_height)), []).append(i)
+    with torch.no_grad():
+        for (W, H), idx in groups.items():
+            cams = [cameras[i] for i in idx]
+            fr = _renderer(model, W, H, cams, bg, batch, capacity)
+            for c0 in range(0, len(cams), batch):
+                outs = _render_checked(fr, cams[c0:c0 + batch], bg)
+                yield idx[c0:c0 + batch], [o["render"] for o in outs]
+
+
+def render_views(model, cameras: Sequence, bg: torch.Tensor, *, batch: int = MAX_BATCH,
+                 capacity: Optional[int] = None) -> List[torch.Tensor]:
+    """render(cam, model, pipe, bg)["render"] under no_grad for every camera, up to `batch` (<= 8) views of the same
+    W x H per launch.  `capacity`: the starting binning capacity of a fresh renderer (default: fit_capacity() on the
+    first batch)."""
+    out: List[Optional[torch.Tensor]] = [None] * len(cameras)
+    for idx, imgs in _batches(model, cameras, bg, batch, capacity):
+        for i, img in zip(idx, imgs):
+            out[i] = img.clone()
+    return out
+
+
+# ---- metrics -----------------------------------------------------------------------------------------------------------
+def image_metrics(images: Sequence[torch.Tensor], gts: Sequence[torch.Tensor], masks=None, mode: int = CLAMP,
+                  prepared: bool = False):
+    """Device sums of b3gs_image_metrics_batch for [C,H,W] pairs of one shape: float64 [n, 2C + 2] (sum |d| per channel,
+    sum d^2 per channel, sum d^2 where mask == 1, that count) and, with `prepared`, the composited pair ([n,C,H,W] each)."""
+    from . import _C
+    n = len(images)
+    C, H, W = images[0].shape
+    dev = images[0].device
+    out = torch.empty((n, 2 * C + 2), dtype=torch.float64, device=dev)
+    pi = pg = None
+    if prepared:
+        pi = torch.empty((n, C, H, W), dtype=torch.float32, device=dev)
+        pg = torch.empty_like(pi)
+    _C.image_metrics(list(images), list(gts), None if masks is None else list(masks), int(mode), out, pi, pg)
+    return out, pi, pg
+
+
+def _psnr(mse):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 20.0 * np.log10(1.0 / np.sqrt(mse))
+
+
+def _device_sums(model, cameras, bg, masks, mode_bits: int, want_ssim: bool, batch: int, capacity=None):
+    """-> (sums [N, 2C+2] float64, ssim [N] or None, H*W per view, C), one read-back at the end."""
+    from . import _C
+    parts = []
+    for idx, imgs in _batches(model, cameras, bg, batch, capacity):
+        gts = [cameras[i].original_image for i in idx]
+        mk = None if masks is None else [masks[i] for i in idx]
+        sums, pi, pg = image_metrics(imgs, gts, mk, mode_bits, prepared=want_ssim)
+        ss = _C.ssim(pi, pg, 11, False) if want_ssim else None
+        parts.append((idx, sums, ss))
+    order = [i for idx, _, _ in parts for i in idx]
+    sums = torch.cat([s for _, s, _ in parts]).cpu().numpy()
+    ssim = torch.cat([s for _, _, s in parts]).double().cpu().numpy() if want_ssim else None
+    inv = np.empty(len(order), dtype=np.int64)
+    inv[np.asarray(order, dtype=np.int64)] = np.arange(len(order))
+    hw = np.array([float(cameras[i].image_width * cameras[i].image_height) for i in range(len(cameras))])
+    return sums[inv], (None if ssim is None else ssim[inv]), hw
+
+
+def evaluate_views(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, mode: str = "report",
+                   batch: int = MAX_BATCH) -> dict:
+    """SSIM / PSNR / L1 of every camera's render against its `original_image`.
+
+    mode "report": both images clamped to [0,1]; PSNR = mean of the per-channel PSNRs (train.py:226-261).
+    mode "png":    both images through the 8-bit PNG round trip, composited with `masks` (per camera None, [1,H,W] or
+                   [3,H,W]; None = LLFF's all-ones mask), PSNR over the elements whose mask is exactly 1 (metrics.py).
+    SSIM is ssim() of the composited pair, L1 the mean |difference| of the same pair.
+    -> {"per_view": [{"SSIM", "PSNR", "L1"}, ...], "SSIM", "PSNR", "L1": fp32 means of the per-view values}."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)}")
+    if not cameras:
+        return {"per_view": [], "SSIM": math.nan, "PSNR": math.nan, "L1": math.nan}
+    sums, ssim, hw = _device_sums(model, cameras, bg, masks, MODES[mode], True, batch)
+    C = (sums.shape[1] - 2) // 2
+    l1 = sums[:, :C].sum(1) / (C * hw)
+    if mode == "report":
+        psnr = _psnr(sums[:, C:2 * C] / hw[:, None]).mean(1)
+    else:
+        psnr = _psnr(sums[:, 2 * C] / sums[:, 2 * C + 1])
+    per_view = [{"SSIM": float(s), "PSNR": float(p), "L1": float(a)} for s, p, a in zip(ssim, psnr, l1)]
+    res = {"per_view": per_view}
+    for key in ("SSIM", "PSNR", "L1"):     # metrics.py:108-110: torch.tensor(values).mean() -- fp32
+        res[key] = float(torch.tensor([v[key] for v in per_view]).mean())
+    return res
+
+
+# ---- training_report (train.py:226-261) --------------------------------------------------------------------------------
+def report_configs(test_cameras, train_cameras):
+    """train.py:235-236: the test cameras, and train cameras 5, 10, .., 25 modulo their count (3 views: 2,1,0,2,1)."""
+    train = list(train_cameras or [])
+    return [("test", list(test_cameras or [])),
+            ("train", [train[i % len(train)] for i in range(5, 30, 5)] if train else [])]
+
+
+def training_report(model, test_cameras, train_cameras, bg: torch.Tensor, *, batch: int = MAX_BATCH,
+                    render_fn: Optional[Callable] = None, view_metrics: Optional[Callable] = None) -> dict:
+    """train.py:238-252 -> {"test": (l1, psnr), "train": (l1, psnr)}; a config without cameras is left out.
+    Per view: clamp(render, 0, 1) against clamp(original_image, 0, 1), L1 and the mean of the per-channel PSNRs, summed in
+    float64 in view order and divided by the camera count.
+
+    Default: render_views + b3gs_image_metrics_batch (fp64 sums).  `render_fn(cameras) -> [3,H,W] images` and
+    `view_metrics(image, gt) -> (l1, psnr)` replace the two halves (the reference's statements, on the CPU)."""
+    res = {}
+    for name, cams in report_configs(test_cameras, train_cameras):
+        if not cams:
+            continue
+        if view_metrics is None:
+            sums, _, hw = _device_sums(model, cams, bg, None, CLAMP, False, batch)
+            C = (sums.shape[1] - 2) // 2
+            vals = zip(sums[:, :C].sum(1) / (C * hw), _psnr(sums[:, C:2 * C] / hw[:, None]).mean(1))
+        else:
+            images = render_fn(cams) if render_fn is not None else render_views(model, cams, bg, batch=batch)
+            vals = [view_metrics(torch.clamp(img, 0.0, 1.0), torch.clamp(cam.original_image, 0.0, 1.0))
+                    for img, cam in zip(images, cams)]
+        l1_sum, psnr_sum = 0.0, 0.0
+        for l1, psnr in vals:
+            l1_sum += float(l1)
+            psnr_sum += float(psnr)
+        res[name] = (l1_sum / len(cams), psnr_sum / len(cams))
+    return res
+
+
+# ---- results.json / per_view.json (metrics.py:105-122) ----------------------------------------------------------------
+def write_results(model_path: str, method: str, per_view: Sequence[dict], names: Sequence[str]) -> dict:
+    """Writes <model_path>/results.json {method: {"SSIM", "PSNR"}} and per_view.json {method: {"SSIM": {name: v}, "PSNR":
+    {name: v}}} in the reference's layout (json.dump, indent=True), without the LPIPS key.  Means are fp32, as
+    torch.tensor(values).mean() is there.  Returns the two dicts."""
+    if len(per_view) != len(names):
+        raise ValueError("one name per view")
+    keys = ("SSIM", "PSNR")
+    vals = {k: torch.tensor([float(v[k]) for v in per_view]) for k in keys}
+    full = {method: {k: vals[k].mean().item() for k in keys}}
+    per = {method: {k: {name: x for x, name in zip(vals[k].tolist(), names)} for k in keys}}
+    os.makedirs(model_path, exist_ok=True)
+    with open(os.path.join(model_path, "results.json"), "w") as fp:
+        json.dump(full, fp, indent=True)
+    with open(os.path.join(model_path, "per_view.json"), "w") as fp:
+        json.dump(per, fp, indent=True)
+    return {"results": full, "per_view": per}

@@ -9,7 +9,9 @@ loss_utils, graphics_utils -- each one HIP launch behind the reference's signatu
 of bench_ref_schedule.py and the lock-step trainer of tests/ref_schedule.py run.
 
 Branches of the reference's loop that are configuration, not call sequence, and are NOT driven here: the DTU background
-mask (train.py:112-120, a dataset switch), random backgrounds, the network GUI, test-view reports, saving.
+mask (train.py:112-120, a dataset switch), random backgrounds, the network GUI, saving.  The test-view report of
+train.py:226-261 is optional (`test_iterations`, default none): evaluate.training_report at the reference's point of the
+iteration, after backward() and before the opacity decay, the densification statistics and optimizer.step().
 """
 from __future__ import annotations
 
@@ -35,7 +37,8 @@ class IterationSchedule:
     def __init__(self, model, scene, pipe, background, *, ops=None, iterations=30_000, shift_cam_start=20_000,
                  binocular=True, opacity_decay_factor=0.995, lambda_dssim=0.2, densify_from_iter=500,
                  densify_until_iter=15_000, densification_interval=100, densify_grad_threshold=0.0002, min_opacity=0.005,
-                 sh_interval=1000, smooth_weight=0.05, log_item=False, before_densify=None):
+                 sh_interval=1000, smooth_weight=0.05, log_item=False, before_densify=None, test_cameras=None,
+                 test_iterations=(), report_fn=None):
         self.model, self.scene, self.pipe, self.background = model, scene, pipe, background
         self.ops = ops if ops is not None else default_ops()
         self.iterations, self.shift_cam_start, self.binocular = iterations, shift_cam_start, binocular
@@ -44,6 +47,9 @@ class IterationSchedule:
         self.densification_interval, self.grad_threshold, self.min_opacity = densification_interval, densify_grad_threshold, \
             min_opacity
         self.sh_interval, self.log_item, self.before_densify = sh_interval, log_item, before_densify
+        # train.py:166 training_report: {iteration: {"test": (l1, psnr), "train": (l1, psnr)}} for every iteration listed
+        self.test_cameras, self.test_iterations = list(test_cameras or []), frozenset(test_iterations)
+        self.report_fn, self.reports = report_fn, {}
         self.views = list(scene.getTrainCameras())
         H, W = self.views[0].image_height, self.views[0].image_width
         dev = background.device
@@ -97,6 +103,11 @@ class IterationSchedule:
 
     def _after_backward(self, it, first):
         m = self.model
+        if it in self.test_iterations:
+            if self.report_fn is None:
+                from .evaluate import training_report
+                self.report_fn = training_report
+            self.reports[it] = self.report_fn(m, self.test_cameras, self.views, self.background)
         if self.decay is not None and it > self.densify_from_iter:
             self.densify_until_iter = self.iterations      # with the decay on, densification runs to the end
             m.opacity_decay(factor=self.decay)

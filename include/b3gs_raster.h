@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 10
+#define B3GS_ABI_VERSION 11
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -473,6 +473,33 @@ int b3gs_apply_staged_densify_stats(int64_t P, float* staged_accum, float* stage
  * step number given by the host (1-based, the value of state["step"] after its increment); no decay, no row mask. */
 int b3gs_adam_step_at(int32_t nseg, const B3gsAdamSegment* segs, int32_t step, float beta1, float beta2, float eps,
                       b3gs_stream_t stream);
+
+/* ---- ABI 11: image metrics of held-out views (binocular3dgs_amd/evaluate.py) -----------------------------------------
+ * The per-view sums behind train.py:226-261 (training_report: clamp to [0,1], mean L1, mean of per-channel PSNRs) and
+ * metrics.py:37-124 over the PNGs of render.py (8-bit round trip, DTU mask composite, masked PSNR, SSIM).  Per view and
+ * element: both images are clamped to [0,1] (mode bit B3GS_METRIC_CLAMP) and/or quantised to
+ * uint8(clamp(x*255 + 0.5, 0, 255)) / 255 (bit B3GS_METRIC_QUANTIZE, torchvision's save_image + to_tensor), then
+ * composited with the mask as x*m + (1 - m) (mask NULL: unchanged), then d = image - gt.
+ * out[v, 2C + 2] (fp64): sum |d| per channel, sum d^2 per channel, sum d^2 over the elements with m == 1 exactly (all
+ * channels pooled; every element when mask is NULL), the number of those elements.
+ * prepared_image / prepared_gt (both NULL or both set): [C,H,W] each, the composited pair -- with one [nviews,C,H,W]
+ * tensor per side, b3gs_ssim_forward(batch = nviews, size_average = 0) gives the per-view SSIM of metrics.py.
+ * One partial-sum launch per 32 views (all views of an evaluation batch in one) and one fold in fixed order: no float
+ * atomics, every sum in fp64, the same bits from call to call.  All images fp32, contiguous, [C,H,W]; 1 <= C <= 4.
+ * workspace: b3gs_image_metrics_workspace_bytes(nviews, C, H, W) bytes, no initial content needed. */
+#define B3GS_METRIC_CLAMP 1
+#define B3GS_METRIC_QUANTIZE 2
+typedef struct B3gsMetricView {
+  const float* image;     /* [C,H,W] */
+  const float* gt;        /* [C,H,W] */
+  const float* mask;      /* NULL, [1,H,W] (broadcast over the channels) or [C,H,W]; may be fractional */
+  int32_t mask_channels;  /* 1 or C (ignored when mask is NULL) */
+  float* prepared_image;  /* NULL or [C,H,W] */
+  float* prepared_gt;     /* NULL or [C,H,W] */
+} B3gsMetricView;
+size_t b3gs_image_metrics_workspace_bytes(int32_t nviews, int32_t C, int32_t H, int32_t W);
+int b3gs_image_metrics_batch(int32_t nviews, const B3gsMetricView* views, int32_t C, int32_t H, int32_t W, int32_t mode,
+                             double* out, void* workspace, b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
