@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("B3GS_LIB") or os.path.join(_HERE, "libb3gs_raster.so")   # B3GS_LIB: A/B builds of the kernels
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 OK = 0
 ERR_NAMES = {-1: "B3GS_ERR_ARG", -2: "B3GS_ERR_ALLOC", -3: "B3GS_ERR_HIP", -4: "B3GS_ERR_CAPACITY",
              -5: "B3GS_ERR_NO_DEVICE"}
@@ -100,6 +100,11 @@ class B3gsMetricView(C.Structure):
                 ("prepared_image", C.c_void_p), ("prepared_gt", C.c_void_p)]
 
 
+class B3gsFrameView(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p), ("rgb_out", C.c_void_p),
+                ("gray_out", C.c_void_p), ("cmap_out", C.c_void_p)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -119,7 +124,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_ssim_backward", "b3gs_opacity_decay", "b3gs_add_densification_stats", "b3gs_adam_step_at", "b3gs_debug_activations",
            "b3gs_apply_staged_densify_stats",
            # ABI 11: image metrics of held-out views
-           "b3gs_image_metrics_workspace_bytes", "b3gs_image_metrics_batch")
+           "b3gs_image_metrics_workspace_bytes", "b3gs_image_metrics_batch",
+           # ABI 12: frames of a rendered path
+           "b3gs_frames_workspace_bytes", "b3gs_encode_frames_batch")
 
 _lib = None
 
@@ -227,6 +234,10 @@ def lib():
     L.b3gs_image_metrics_workspace_bytes.restype = C.c_size_t
     L.b3gs_image_metrics_batch.argtypes = [I32, C.POINTER(B3gsMetricView), I32, I32, I32, I32, V, V, V]
     L.b3gs_image_metrics_batch.restype = C.c_int
+    L.b3gs_frames_workspace_bytes.argtypes = [I32, I32, I32]
+    L.b3gs_frames_workspace_bytes.restype = C.c_size_t
+    L.b3gs_encode_frames_batch.argtypes = [I32, C.POINTER(B3gsFrameView), I32, I32, C.c_double, V, V, V, V]
+    L.b3gs_encode_frames_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

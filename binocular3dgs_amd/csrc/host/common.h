@@ -52,5 +52,6 @@ void bind_loss(pybind11::module_& m);
 void bind_optim(pybind11::module_& m);
 void bind_raster(pybind11::module_& m);
 void bind_metrics(pybind11::module_& m);
+void bind_frames(pybind11::module_& m);
 
 }  // namespace b3

@@ -70,8 +70,9 @@ def _render_checked(fr, cams: Sequence, bg: torch.Tensor) -> List[dict]:
     raise RuntimeError("evaluation render: the binning capacity still overflowed after growing twice")
 
 
-def _batches(model, cameras: Sequence, bg: torch.Tensor, batch: int, capacity: Optional[int] = None):
-    """Yields (indices into `cameras`, [3,H,W] images) per launch, views of one W x H together.  The images are the
+def _batches(model, cameras: Sequence, bg: torch.Tensor, batch: int, capacity: Optional[int] = None, full: bool = False):
+    """Yields (indices into `cameras`, [3,H,W] images) per launch, views of one W x H together; with `full`, the per-view
+    output dicts of the render ("render", "rendered_depth", "rendered_alpha", ...) instead of the images.  Both are the
     renderer's slot buffers: valid until the next item is drawn."""
     batch = max(1, min(int(batch), MAX_BATCH))
     groups: Dict[tuple, List[int]] = {}
@@ -83,7 +84,7 @@ def _batches(model, cameras: Sequence, bg: torch.Tensor, batch: int, capacity: O
             fr = _renderer(model, W, H, cams, bg, batch, capacity)
             for c0 in range(0, len(cams), batch):
                 outs = _render_checked(fr, cams[c0:c0 + batch], bg)
-                yield idx[c0:c0 + batch], [o["render"] for o in outs]
+                yield idx[c0:c0 + batch], (outs if full else [o["render"] for o in outs])
 
 
 def render_views(model, cameras: Sequence, bg: torch.Tensor, *, batch: int = MAX_BATCH,

@@ -1,0 +1,96 @@
+"""python -m binocular3dgs_amd.spiral -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--resolution R] [--white_background]
+
+The reference's spiral.py: the trained point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply, rendered along the
+180-frame spiral of <source_path>/poses_bounds.npy (DTU when the source path contains 'scan'), written as %05d.png,
+depth_%05d.png and cdepth_%05d.png to <model_path>/render/ours_<it>/.  Renders and frame encoding run in batches on the
+device (frames.render_path); video encoding is left to the user (the ffmpeg lines are printed).
+
+Defaults for source_path, sh_degree, resolution and white_background come from <model_path>/cfg_args when it exists (the
+Namespace(...) line train.py writes, read with `ast`: literals only, nothing is executed); the command line wins.
+"""
+from __future__ import annotations
+
+import argparse
+import ast
+import os
+import sys
+import time
+
+import torch
+
+
+def read_cfg_args(model_path: str) -> dict:
+    """The keyword literals of <model_path>/cfg_args ("Namespace(k=v, ...)"); {} when missing or not of that form."""
+    path = os.path.join(model_path, "cfg_args")
+    if not os.path.exists(path):
+        return {}
+    with open(path) as fp:
+        text = fp.read()
+    try:
+        node = ast.parse(text.strip(), mode="eval").body
+    except SyntaxError:
+        return {}
+    if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "Namespace"):
+        return {}
+    out = {}
+    for kw in node.keywords:
+        try:
+            out[kw.arg] = ast.literal_eval(kw.value)
+        except ValueError:
+            pass
+    return out
+
+
+def max_iteration(model_path: str) -> int:
+    """utils/system_utils.py searchForMaxIteration over <model_path>/point_cloud/iteration_<n>."""
+    names = os.listdir(os.path.join(model_path, "point_cloud"))
+    its = [int(n.split("_")[-1]) for n in names if n.startswith("iteration_")]
+    if not its:
+        raise FileNotFoundError(f"no point_cloud/iteration_* under {model_path}")
+    return max(its)
+
+
+def run(model_path: str, source_path: str = None, iteration: int = -1, resolution=None, white_background=None,
+        sh_degree=None, n_frames: int = 180) -> str:
+    from . import camera_path, frames
+    from .gaussian_model import GaussianModel
+    cfg = read_cfg_args(model_path)
+    source_path = source_path or cfg.get("source_path")
+    if not source_path:
+        raise ValueError("no source path: pass -s or keep cfg_args next to the model")
+    resolution = resolution if resolution is not None else cfg.get("resolution", -1)
+    white = white_background if white_background is not None else bool(cfg.get("white_background", False))
+    sh = sh_degree if sh_degree is not None else int(cfg.get("sh_degree", 1))
+    it = max_iteration(model_path) if iteration == -1 else iteration
+    model = GaussianModel(sh)
+    model.load_ply(os.path.join(model_path, "point_cloud", "iteration_" + str(it), "point_cloud.ply"))
+    cams = camera_path.spiral_cameras_from_dir(source_path, n_frames=n_frames, resolution=resolution, device="cuda")
+    bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
+    out_dir = os.path.join(model_path, "render", "ours_{}".format(it))
+    t0 = time.perf_counter()
+    frames.render_path(model, cams, bg, out_dir)
+    dt = time.perf_counter() - t0
+    print(f"{len(cams)} frames ({cams[0].image_width}x{cams[0].image_height}) -> {out_dir} in {dt:.2f} s")
+    scene = os.path.basename(os.path.normpath(source_path))
+    print("video (not encoded here):")
+    for pat, out in (("%05d.png", "out_{}.mp4"), ("depth_%05d.png", "out_depth_{}.mp4"), ("cdepth_%05d.png", "out_cdepth_{}.mp4")):
+        print(f"  ffmpeg -i {os.path.join(out_dir, pat)} -q 2 {os.path.join(model_path, out.format(scene))} -y")
+    return out_dir
+
+
+def main(argv=None) -> int:
+    p = argparse.ArgumentParser(description="render the spiral path of a trained model (spiral.py)")
+    p.add_argument("-m", "--model_path", required=True)
+    p.add_argument("-s", "--source_path", default=None)
+    p.add_argument("--iteration", type=int, default=-1)
+    p.add_argument("-r", "--resolution", type=int, default=None)
+    p.add_argument("-w", "--white_background", action="store_true", default=None)
+    p.add_argument("--sh_degree", type=int, default=None)
+    p.add_argument("--frames", type=int, default=180, help="frames of the spiral (the reference: 180)")
+    a = p.parse_args(argv)
+    run(a.model_path, a.source_path, a.iteration, a.resolution, a.white_background, a.sh_degree, a.frames)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 11
+#define B3GS_ABI_VERSION 12
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -500,6 +500,38 @@ typedef struct B3gsMetricView {
 size_t b3gs_image_metrics_workspace_bytes(int32_t nviews, int32_t C, int32_t H, int32_t W);
 int b3gs_image_metrics_batch(int32_t nviews, const B3gsMetricView* views, int32_t C, int32_t H, int32_t W, int32_t mode,
                              double* out, void* workspace, b3gs_stream_t stream);
+
+/* ---- ABI 12: frames of a rendered path (binocular3dgs_amd/frames.py) --------------------------------------------------
+ * The three uint8 images spiral.py:101-131 writes per frame, bit for bit, with torchvision's quantiser
+ * q(x) = uint8(clamp(x*255 + 0.5, 0, 255)):
+ *   rgb_out   [H,W,3]  q(rgb), fp32
+ *   gray_out  [H,W,3]  v = 1 - (1 - (depth - min) / (max - min)) * alpha (fp32, that op order, min / max over all H*W
+ *                      pixels of the view), q(v) in all three channels
+ *   cmap_out  [H,W,3]  visualize_cmap(v, ones, turbo, percentile, curve -log(x + 1e-6)): lo / hi are the weighted
+ *                      percentiles 50 -/+ percentile/2 of v (np.interp on the exact order statistics), widened by the fp32
+ *                      epsilon; the value is curved in fp32, lo / hi in fp64, normalised in fp64, clipped, NaN -> 0, LUT
+ *                      index int(x*256) with 256 -> 255; the pixel is lut[index] (lut: 256 x 3 bytes on the device).
+ * Empty view (max == min: the reference divides 0 by 0): gray 0 and cmap lut[0] everywhere, bounds NaN.
+ * depth must be finite.  Any of the three outputs may be NULL (skipped); rgb may be NULL when rgb_out is, depth / alpha
+ * when gray_out and cmap_out are (and bounds_out is NULL).
+ * bounds_out: NULL or device double[nviews * 2]: the percentile bounds lo_auto, hi_auto of every view (before the
+ * epsilon and the curve).
+ * Exact and deterministic: min / max by comparison, the order statistics by an exact radix select (11/11/10 bits, integer
+ * atomics on histograms only).  8 launches per call whatever nviews; the host reads nothing.
+ * 1 <= nviews <= 8, 1 <= H*W <= 2^24 (the reference's fp32 cumulative weights are exact integers there).
+ * workspace: b3gs_frames_workspace_bytes(nviews, H, W) bytes, no initial content needed. */
+#define B3GS_MAX_FRAME_VIEWS 8
+typedef struct B3gsFrameView {
+  const float* rgb;    /* [3,H,W] */
+  const float* depth;  /* [1,H,W] */
+  const float* alpha;  /* [1,H,W] */
+  uint8_t* rgb_out;    /* NULL or [H,W,3] */
+  uint8_t* gray_out;   /* NULL or [H,W,3] */
+  uint8_t* cmap_out;   /* NULL or [H,W,3] */
+} B3gsFrameView;
+size_t b3gs_frames_workspace_bytes(int32_t nviews, int32_t H, int32_t W);
+int b3gs_encode_frames_batch(int32_t nviews, const B3gsFrameView* views, int32_t H, int32_t W, double percentile,
+                             const uint8_t* lut, void* workspace, double* bounds_out, b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
