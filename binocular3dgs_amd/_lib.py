@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("B3GS_LIB") or os.path.join(_HERE, "libb3gs_raster.so")   # B3GS_LIB: A/B builds of the kernels
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 OK = 0
 ERR_NAMES = {-1: "B3GS_ERR_ARG", -2: "B3GS_ERR_ALLOC", -3: "B3GS_ERR_HIP", -4: "B3GS_ERR_CAPACITY",
              -5: "B3GS_ERR_NO_DEVICE"}
@@ -105,6 +105,12 @@ class B3gsFrameView(C.Structure):
                 ("gray_out", C.c_void_p), ("cmap_out", C.c_void_p)]
 
 
+class B3gsGtView(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("C", C.c_int32), ("tab_x", C.c_void_p),
+                ("tab_y", C.c_void_p), ("ks_x", C.c_int32), ("ks_y", C.c_int32), ("image", C.c_void_p),
+                ("alpha", C.c_void_p), ("bg_mask", C.c_void_p)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -126,7 +132,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # ABI 11: image metrics of held-out views
            "b3gs_image_metrics_workspace_bytes", "b3gs_image_metrics_batch",
            # ABI 12: frames of a rendered path
-           "b3gs_frames_workspace_bytes", "b3gs_encode_frames_batch")
+           "b3gs_frames_workspace_bytes", "b3gs_encode_frames_batch",
+           # ABI 13: ground-truth preparation of dataset images
+           "b3gs_gt_workspace_bytes", "b3gs_prepare_gt_batch")
 
 _lib = None
 
@@ -238,6 +246,10 @@ def lib():
     L.b3gs_frames_workspace_bytes.restype = C.c_size_t
     L.b3gs_encode_frames_batch.argtypes = [I32, C.POINTER(B3gsFrameView), I32, I32, C.c_double, V, V, V, V]
     L.b3gs_encode_frames_batch.restype = C.c_int
+    L.b3gs_gt_workspace_bytes.argtypes = [I32, C.POINTER(B3gsGtView), I32, I32]
+    L.b3gs_gt_workspace_bytes.restype = C.c_size_t
+    L.b3gs_prepare_gt_batch.argtypes = [I32, C.POINTER(B3gsGtView), I32, I32, I32, C.c_float, V, V]
+    L.b3gs_prepare_gt_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -106,8 +106,15 @@ class Camera:
     znear = 0.01
 
     def __init__(self, R, T, FoVx, FoVy, width, height, image=None, gt_alpha_mask=None, uid=0,
-                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, device="cpu"):
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, device="cpu", *, prepared=False, image_name=None,
+                 colmap_id=None, bg_mask=None):
+        """`prepared=True`: `image` / `gt_alpha_mask` are final already (ground_truth.prepare_ground_truth: clamped and
+        multiplied by the mask on the device) and are attached as they are.  `bg_mask`: the DTU background mask
+        (train.py:110-120) of this view, computed once."""
         self.uid = uid
+        self.colmap_id = colmap_id
+        self.image_name = image_name
+        self.bg_mask = bg_mask
         self.R = np.asarray(R, dtype=np.float64)
         self.T = np.asarray(T, dtype=np.float64)
         self.FoVx = float(FoVx)
@@ -117,10 +124,14 @@ class Camera:
         self.trans = np.asarray(trans, dtype=np.float64)
         self.scale = scale
         self.device = torch.device(device)
-        self.original_image = None if image is None else image.clamp(0.0, 1.0).to(self.device)
-        self.gt_alpha_mask = None if gt_alpha_mask is None else gt_alpha_mask.to(self.device)
-        if self.original_image is not None and self.gt_alpha_mask is not None:
-            self.original_image = self.original_image * self.gt_alpha_mask
+        if prepared:
+            self.original_image = None if image is None else image.to(self.device)
+            self.gt_alpha_mask = None if gt_alpha_mask is None else gt_alpha_mask.to(self.device)
+        else:
+            self.original_image = None if image is None else image.clamp(0.0, 1.0).to(self.device)
+            self.gt_alpha_mask = None if gt_alpha_mask is None else gt_alpha_mask.to(self.device)
+            if self.original_image is not None and self.gt_alpha_mask is not None:
+                self.original_image = self.original_image * self.gt_alpha_mask
         wvt = torch.tensor(world_to_view(self.R, self.T, self.trans, scale)).transpose(0, 1)
         proj = projection_matrix(self.znear, self.zfar, self.FoVx, self.FoVy).transpose(0, 1)
         self._set(wvt, proj)

@@ -134,15 +134,10 @@ def _world_to_camera(path: np.ndarray) -> Tuple[np.ndarray, np.ndarray, float, f
 
 
 def render_size(orig_w: float, orig_h: float, resolution) -> Tuple[int, int]:
-    """utils/camera_utils.py:69-90 (loadRenderCam) at resolution_scale 1."""
-    if resolution in [1, 2, 4, 8]:
-        return round(orig_w / (1.0 * resolution)), round(orig_h / (1.0 * resolution))
-    if resolution == -1:
-        down = orig_w / 6400 if orig_w > 6400 else 1
-    else:
-        down = orig_w / resolution
-    scale = float(down) * 1.0
-    return int(orig_w / scale), int(orig_h / scale)
+    """utils/camera_utils.py:69-90 (loadRenderCam) at resolution_scale 1: loadCam's rule (ground_truth.scaled_size) with the
+    width cap of resolution -1 at 6400."""
+    from .ground_truth import scaled_size
+    return scaled_size(orig_w, orig_h, resolution, 6400)
 
 
 def spiral_cameras(poses_bounds: np.ndarray, *, dtu: bool, n_frames: int = 180, resolution=1,

@@ -138,6 +138,77 @@ def write_png(path: str, hwc_uint8, level: int = 6) -> str:
     return path
 
 
+_PNG_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}      # colour type -> samples per pixel (3 = palette: not read)
+
+
+def png_size(path: str):
+    """(width, height) from the IHDR chunk of a PNG file."""
+    with open(path, "rb") as fp:
+        head = fp.read(24)
+    if head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        raise ValueError(f"{path}: not a PNG file")
+    return struct.unpack(">II", head[16:24])
+
+
+def read_png(path: str) -> np.ndarray:
+    """uint8 [H,W] (gray), [H,W,2] (gray + alpha), [H,W,3] or [H,W,4] of an 8-bit, non-interlaced PNG; stdlib zlib + struct and
+    the five row filters.  Palette, 16-bit, sub-byte and interlaced files raise ValueError."""
+    with open(path, "rb") as fp:
+        data = fp.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG file")
+    pos, idat, header = 8, [], None
+    while pos + 8 <= len(data):
+        n, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if kind == b"IHDR":
+            header = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+        pos += 12 + n
+    if header is None:
+        raise ValueError(f"{path}: no IHDR chunk")
+    W, H, depth, ctype, _comp, _filt, interlace = header
+    if depth != 8 or ctype not in _PNG_CHANNELS or interlace != 0:
+        raise ValueError(f"{path}: only 8-bit non-interlaced gray / gray+alpha / RGB / RGBA PNGs are read "
+                         f"(bit depth {depth}, colour type {ctype}, interlace {interlace})")
+    bpp = _PNG_CHANNELS[ctype]
+    stride = W * bpp
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), dtype=np.uint8)
+    if raw.size != H * (stride + 1):
+        raise ValueError(f"{path}: {raw.size} bytes of image data for {H} rows of {stride + 1}")
+    raw = raw.reshape(H, stride + 1)
+    out = np.zeros((H, stride), dtype=np.uint8)
+    zero = np.zeros(stride, dtype=np.uint8)
+    for y in range(H):
+        f, line = int(raw[y, 0]), raw[y, 1:]
+        up = out[y - 1] if y else zero
+        if f == 0:
+            out[y] = line
+        elif f == 2:
+            out[y] = line + up
+        elif f == 1:                                   # left neighbour: a running sum per sample position (mod 256)
+            out[y] = np.cumsum(line.reshape(W, bpp), axis=0, dtype=np.uint8).reshape(-1)
+        elif f in (3, 4):                              # depend on the reconstructed left neighbour: pixel by pixel
+            cur, ln, upl = [0] * stride, line.tolist(), up.tolist()
+            for i in range(stride):
+                a = cur[i - bpp] if i >= bpp else 0
+                b = upl[i]
+                if f == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = upl[i - bpp] if i >= bpp else 0
+                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+                    pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
+                cur[i] = (ln[i] + pred) & 255
+            out[y] = cur
+        else:
+            raise ValueError(f"{path}: row filter {f}")
+    return out.reshape(H, W) if bpp == 1 else out.reshape(H, W, bpp)
+
+
 # ---- drivers -----------------------------------------------------------------------------------------------------------
 def render_path(model, cameras: Sequence, bg: torch.Tensor, out_dir: Optional[str] = None, *, batch: int = MAX_BATCH,
                 percentile: float = 99.):

@@ -8,8 +8,11 @@ G11 event for event when handed the same stand-ins.  With the default `ops` it d
 loss_utils, graphics_utils -- each one HIP launch behind the reference's signature), which is what the "unchanged" surface
 of bench_ref_schedule.py and the lock-step trainer of tests/ref_schedule.py run.
 
-Branches of the reference's loop that are configuration, not call sequence, and are NOT driven here: the DTU background
-mask (train.py:112-120, a dataset switch), random backgrounds, the network GUI, saving.  The test-view report of
+The DTU background mask (train.py:110-120, 139-143) is driven from the camera: a view that carries a `bg_mask` (computed
+once per camera by ground_truth.prepare_ground_truth, not 49 launches per iteration) and no alpha mask adds
+mean(|alpha| * bg_mask) to the loss; cameras without the attribute behave as before.  Branches that are configuration, not
+call sequence, and are NOT driven here: random backgrounds (the caller hands in `background`), the network GUI, saving
+(binocular3dgs_amd/train.py does).  The test-view report of
 train.py:226-261 is optional (`test_iterations`, default none): evaluate.training_report at the reference's point of the
 iteration, after backward() and before the opacity decay, the densification statistics and optimizer.step().
 """
@@ -38,7 +41,7 @@ class IterationSchedule:
                  binocular=True, opacity_decay_factor=0.995, lambda_dssim=0.2, densify_from_iter=500,
                  densify_until_iter=15_000, densification_interval=100, densify_grad_threshold=0.0002, min_opacity=0.005,
                  sh_interval=1000, smooth_weight=0.05, log_item=False, before_densify=None, test_cameras=None,
-                 test_iterations=(), report_fn=None):
+                 test_iterations=(), report_fn=None, after_report=None):
         self.model, self.scene, self.pipe, self.background = model, scene, pipe, background
         self.ops = ops if ops is not None else default_ops()
         self.iterations, self.shift_cam_start, self.binocular = iterations, shift_cam_start, binocular
@@ -50,6 +53,7 @@ class IterationSchedule:
         # train.py:166 training_report: {iteration: {"test": (l1, psnr), "train": (l1, psnr)}} for every iteration listed
         self.test_cameras, self.test_iterations = list(test_cameras or []), frozenset(test_iterations)
         self.report_fn, self.reports = report_fn, {}
+        self.after_report = after_report    # called with the iteration at train.py:166-169 (the point where it saves)
         self.views = list(scene.getTrainCameras())
         H, W = self.views[0].image_height, self.views[0].image_width
         dev = background.device
@@ -90,6 +94,8 @@ class IterationSchedule:
         coverage = 0.0
         if getattr(cam, "gt_alpha_mask", None) is not None:
             coverage = (first["rendered_alpha"].abs() * (1 - cam.gt_alpha_mask)).mean()
+        elif getattr(cam, "bg_mask", None) is not None:
+            coverage = (first["rendered_alpha"].abs() * cam.bg_mask).mean()
         photo = ops.l1_loss(first["render"], target)
         recon = (1.0 - self.lam) * photo + self.lam * (1.0 - ops.ssim(first["render"], target))
         total = recon + stereo + coverage
@@ -108,6 +114,8 @@ class IterationSchedule:
                 from .evaluate import training_report
                 self.report_fn = training_report
             self.reports[it] = self.report_fn(m, self.test_cameras, self.views, self.background)
+        if self.after_report is not None:
+            self.after_report(it)
         if self.decay is not None and it > self.densify_from_iter:
             self.densify_until_iter = self.iterations      # with the decay on, densification runs to the end
             m.opacity_decay(factor=self.decay)

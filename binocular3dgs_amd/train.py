@@ -1,0 +1,160 @@
+"""python -m binocular3dgs_amd.train -s SOURCE_PATH -m MODEL_PATH [--eval --n_views 3 --dataset_name LLFF ...]
+
+The reference's train.py: a COLMAP / Blender dataset folder in, a trained model out.
+
+    Scene.from_dataset     readers on the host, ground truth (and the DTU background mask) prepared on the device
+    IterationSchedule      the iteration of train.py:65-202, every statement a HIP launch of this build
+    per iteration          random.choice(views); past --shift_cam_start: torch.rand(1) * cam_trans_dist and a random sign
+                           (train.py:92,125-126, the same draws from the same generators)
+    --test_iterations      evaluate.training_report's "[ITER n] Evaluating test|train: L1 .. PSNR .." lines
+    --save_iterations      <model_path>/point_cloud/iteration_<n>/point_cloud.ply (before the optimiser step, as there)
+    --checkpoint_iterations / --start_checkpoint   <model_path>/chkpnt<n>.pth (checkpoint.py: the reference's tuple)
+
+<model_path>/cfg_args holds the Namespace(...) line the reference writes; `python -m binocular3dgs_amd.spiral -m MODEL_PATH`
+and evaluate.write_results read the result without further arguments.  No progress bar, no tensorboard, no network GUI.
+`run(args)` is the importable form: `run(parser().parse_args([...]))`.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import random
+import sys
+import uuid
+
+import numpy as np
+import torch
+
+
+def parser() -> argparse.ArgumentParser:
+    """The flags of the reference's train.py that mean something here, with its defaults (arguments/__init__.py,
+    train.py:264-281)."""
+    p = argparse.ArgumentParser(description="train a Binocular3DGS model from a dataset folder")
+    g = p.add_argument_group("loading")
+    g.add_argument("--sh_degree", type=int, default=1)
+    g.add_argument("--source_path", "-s", type=str, default="")
+    g.add_argument("--model_path", "-m", type=str, default="")
+    g.add_argument("--images", "-i", type=str, default="images")
+    g.add_argument("--resolution", "-r", type=int, default=-1)
+    g.add_argument("--white_background", "-w", action="store_true", default=False)
+    g.add_argument("--data_device", type=str, default="cuda")
+    g.add_argument("--eval", action="store_true", default=False)
+    g.add_argument("--init_points", type=str, default="matcher",
+                   help='"matcher" (the dense matcher\'s cloud, the reference\'s rule), "sparse" (COLMAP points3D) or a PLY path')
+    g = p.add_argument_group("optimisation")
+    g.add_argument("--iterations", type=int, default=30_000)
+    g.add_argument("--position_lr_init", type=float, default=0.00016)
+    g.add_argument("--position_lr_final", type=float, default=0.0000016)
+    g.add_argument("--position_lr_delay_mult", type=float, default=0.01)
+    g.add_argument("--position_lr_max_steps", type=int, default=30_000)
+    g.add_argument("--feature_lr", type=float, default=0.0025)
+    g.add_argument("--opacity_lr", type=float, default=0.05)
+    g.add_argument("--scaling_lr", type=float, default=0.005)
+    g.add_argument("--rotation_lr", type=float, default=0.001)
+    g.add_argument("--percent_dense", type=float, default=0.01)
+    g.add_argument("--lambda_dssim", type=float, default=0.2)
+    g.add_argument("--densification_interval", type=int, default=100)
+    g.add_argument("--opacity_reset_interval", type=int, default=3000)
+    g.add_argument("--densify_from_iter", type=int, default=500)
+    g.add_argument("--densify_until_iter", type=int, default=15_000)
+    g.add_argument("--densify_grad_threshold", type=float, default=0.0002)
+    g.add_argument("--random_background", action="store_true", default=False)
+    p.add_argument("--test_iterations", nargs="+", type=int, default=[30_000])
+    p.add_argument("--save_iterations", nargs="+", type=int, default=[30_000])
+    p.add_argument("--quiet", action="store_true")
+    p.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[])
+    p.add_argument("--start_checkpoint", type=str, default=None)
+    p.add_argument("--opacity_decay", action="store_true", default=True)
+    p.add_argument("--opacity_decay_factor", type=float, default=0.995)
+    p.add_argument("--cam_trans_dist", type=float, default=0.4)
+    p.add_argument("--binocular_consistency", action="store_true", default=True)
+    p.add_argument("--shift_cam_start", type=int, default=20000)
+    p.add_argument("--dataset_name", type=str, default="LLFF")
+    p.add_argument("--n_views", type=int, default=3)
+    p.add_argument("--suffix", type=str, default=None)
+    p.add_argument("--seed", type=int, default=0)
+    return p
+
+
+def cfg_args_text(args) -> str:
+    """The line the reference writes to <model_path>/cfg_args (spiral.read_cfg_args parses it)"""
+    return str(argparse.Namespace(**vars(args)))
+
+
+def run(args) -> dict:
+    """Trains; -> {"model_path", "first_iteration", "iterations", "loss" (the last total loss), "points", "reports"}."""
+    from . import checkpoint
+    from .gaussian_model import GaussianModel
+    from .render import PipelineParams
+    from .scene import Scene
+    from .schedule import IterationSchedule
+    args = argparse.Namespace(**vars(args))
+    say = (lambda *a, **k: None) if args.quiet else print
+    args.source_path = os.path.abspath(args.source_path)
+    args.save_iterations = list(args.save_iterations) + [args.iterations]
+    if not args.model_path:
+        args.model_path = os.path.join("./output/", str(uuid.uuid4())[0:10])
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    say("Output folder: {}".format(args.model_path))
+    os.makedirs(args.model_path, exist_ok=True)
+    with open(os.path.join(args.model_path, "cfg_args"), "w") as fp:
+        fp.write(cfg_args_text(args))
+
+    dev = torch.device("cuda")
+    model = GaussianModel(args.sh_degree)
+    scene = Scene.from_dataset(args.source_path, model, images=args.images, eval=args.eval, n_views=args.n_views,
+                               dataset_name=args.dataset_name, suffix=args.suffix, resolution=args.resolution,
+                               white_background=args.white_background, init_points=args.init_points,
+                               model_path=args.model_path, device=dev)
+    model.training_setup(args)
+    first_iter = 0
+    if args.start_checkpoint:
+        model_params, first_iter = checkpoint.load(args.start_checkpoint)
+        model.restore(model_params, args)
+    background = torch.tensor([1, 1, 1] if args.white_background else [0, 0, 0], dtype=torch.float32, device=dev)
+
+    def after_report(it):
+        for name, (l1, psnr) in sched.reports.get(it, {}).items():
+            say("\n[ITER {}] Evaluating {}: L1 {} PSNR {}".format(it, name, l1, psnr))
+        if it in args.save_iterations:
+            say("\n[ITER {}] Saving Gaussians".format(it))
+            scene.save(it)
+
+    sched = IterationSchedule(model, scene, PipelineParams(), background, iterations=args.iterations,
+                              shift_cam_start=args.shift_cam_start, binocular=args.binocular_consistency,
+                              opacity_decay_factor=args.opacity_decay_factor if args.opacity_decay else None,
+                              lambda_dssim=args.lambda_dssim, densify_from_iter=args.densify_from_iter,
+                              densify_until_iter=args.densify_until_iter, densification_interval=args.densification_interval,
+                              densify_grad_threshold=args.densify_grad_threshold, test_cameras=scene.getTestCameras(),
+                              test_iterations=args.test_iterations, after_report=after_report)
+    views = sched.views
+    loss = None
+    for it in range(first_iter + 1, args.iterations + 1):
+        cam = random.choice(views)
+        sched.background = torch.rand((3), device=dev) if args.random_background else background
+        shift = None
+        if args.binocular_consistency and it > args.shift_cam_start:
+            shift = torch.rand(1) * args.cam_trans_dist
+            shift = (shift * random.choice([-1.0, 1.0])).item()
+        loss = sched.run_iteration(it, views.index(cam), shift)
+        if it in args.checkpoint_iterations:
+            say("\n[ITER {}] Saving Checkpoint".format(it))
+            checkpoint.save(args.model_path + "/chkpnt" + str(it) + ".pth", model, model.optimizer, it)
+    say("\nTraining complete.")
+    return {"model_path": args.model_path, "first_iteration": first_iter + 1, "iterations": args.iterations,
+            "loss": None if loss is None else float(loss.detach()), "points": int(model.get_xyz.shape[0]), "reports": dict(sched.reports),
+            "scene": scene, "model": model}
+
+
+def main(argv=None) -> int:
+    args = parser().parse_args(argv)
+    say = (lambda *a: None) if args.quiet else print
+    say("Optimizing " + args.model_path)
+    run(args)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 12
+#define B3GS_ABI_VERSION 13
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -532,6 +532,41 @@ typedef struct B3gsFrameView {
 size_t b3gs_frames_workspace_bytes(int32_t nviews, int32_t H, int32_t W);
 int b3gs_encode_frames_batch(int32_t nviews, const B3gsFrameView* views, int32_t H, int32_t W, double percentile,
                              const uint8_t* lut, void* workspace, double* bounds_out, b3gs_stream_t stream);
+
+/* ---- ABI 13: ground-truth preparation of dataset images (binocular3dgs_amd/ground_truth.py) ----------------------------
+ * From the uint8 source image at its own size to the tensors the training loop reads, bit for bit what the reference
+ * computes on the host (utils/general_utils.py:22-28 PILtoTorch, utils/camera_utils.py:22-57 loadCam,
+ * scene/cameras.py:40-47, train.py:110-120), for up to 8 views of one output W x H per call:
+ *   1. PIL.Image.resize((W, H)) with its default filter, 8 bits per channel: per axis whose size changes, a pass
+ *      clip8((2^21 + sum_j pixel[first + j] * K[j]) >> 22) with the taps of a host-built table; horizontal pass first, stored
+ *      as uint8; RGBA is premultiplied before (c' = ((t >> 8) + t) >> 8, t = c*a + 128) and un-premultiplied after
+ *      (a in {0, 255}: c', else min(255, 255*c' / a)); both sizes unchanged: the source as it is.
+ *   2. / 255 (the correctly rounded fp32 division).  C = 4: alpha = a / 255; with white_background
+ *      image = image * alpha + (1 - alpha) (three roundings, no FMA).  clamp(0, 1).  C = 4: image *= alpha.
+ *   3. dtu_threshold > 0: bg_mask[y, x] = AND over rows max(0, y-49)..y of (max over channels of image < dtu_threshold).
+ * A table is device int32 [2 + ks][out], row-major: row 0 = first source index of every output index, row 1 = its tap
+ * count (<= ks), rows 2.. = the taps with 22 fractional bits (0 beyond the count).  tab_x / tab_y is NULL exactly when
+ * Ws == W / Hs == H.  The caller guarantees 255 * sum|K| < 2^31 per output index (int32 accumulators); source indices are
+ * clamped on the device, so a wrong table gives wrong pixels, never an access outside the buffers.
+ * Outputs (float32, device, 16-byte aligned): image [3,H,W] ([1,H,W] when C = 1), alpha [1,H,W] (C = 4 only, else ignored),
+ * bg_mask [1,H,W] (needed when dtu_threshold > 0).  src is 16-byte aligned.
+ * At most 3 launches per call (horizontal pass only when a view needs it, mask only when asked); the host reads nothing.
+ * workspace: b3gs_gt_workspace_bytes(nviews, views, H, W) bytes (the horizontal passes' intermediates), 256-byte aligned,
+ * no initial content needed. */
+#define B3GS_MAX_GT_VIEWS 8
+typedef struct B3gsGtView {
+  const uint8_t* src;    /* [Hs, Ws, C] */
+  int32_t Hs, Ws, C;     /* C in {1, 3, 4} */
+  const int32_t* tab_x;  /* [2 + ks_x][W] or NULL */
+  const int32_t* tab_y;  /* [2 + ks_y][H] or NULL */
+  int32_t ks_x, ks_y;
+  float* image;
+  float* alpha;
+  float* bg_mask;
+} B3gsGtView;
+size_t b3gs_gt_workspace_bytes(int32_t nviews, const B3gsGtView* views, int32_t H, int32_t W);
+int b3gs_prepare_gt_batch(int32_t nviews, const B3gsGtView* views, int32_t H, int32_t W, int32_t white_background,
+                          float dtu_threshold, void* workspace, b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
