@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("B3GS_LIB") or os.path.join(_HERE, "libb3gs_raster.so")   # B3GS_LIB: A/B builds of the kernels
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 OK = 0
 ERR_NAMES = {-1: "B3GS_ERR_ARG", -2: "B3GS_ERR_ALLOC", -3: "B3GS_ERR_HIP", -4: "B3GS_ERR_CAPACITY",
              -5: "B3GS_ERR_NO_DEVICE"}
@@ -111,6 +111,14 @@ class B3gsGtView(C.Structure):
                 ("alpha", C.c_void_p), ("bg_mask", C.c_void_p)]
 
 
+class B3gsCloudGrow(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("W", "H", "n_views", "ref", "src", "n_seeds", "n_samples", "n_start", "h_patch_size", "init")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "alpha", "ssim_threshold")]
+                + [(n, C.c_void_p) for n in ("images", "w2c", "window", "seed_idx", "noise", "points", "colors")]
+                + [("capacity", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("length", "overflow", "grids", "workspace", "debug_ssim", "debug_mask")])
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -134,7 +142,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # ABI 12: frames of a rendered path
            "b3gs_frames_workspace_bytes", "b3gs_encode_frames_batch",
            # ABI 13: ground-truth preparation of dataset images
-           "b3gs_gt_workspace_bytes", "b3gs_prepare_gt_batch")
+           "b3gs_gt_workspace_bytes", "b3gs_prepare_gt_batch",
+           # ABI 14: the matcher cloud
+           "b3gs_cloud_workspace_bytes", "b3gs_triangulate_matches", "b3gs_background_sheet", "b3gs_cloud_grow_round")
 
 _lib = None
 
@@ -250,6 +260,14 @@ def lib():
     L.b3gs_gt_workspace_bytes.restype = C.c_size_t
     L.b3gs_prepare_gt_batch.argtypes = [I32, C.POINTER(B3gsGtView), I32, I32, I32, C.c_float, V, V]
     L.b3gs_prepare_gt_batch.restype = C.c_int
+    L.b3gs_cloud_workspace_bytes.argtypes = [I64]
+    L.b3gs_cloud_workspace_bytes.restype = C.c_size_t
+    L.b3gs_triangulate_matches.argtypes = [I32] + [V] * 8 + [I32, I32, F, V, V, V, V, V]
+    L.b3gs_triangulate_matches.restype = C.c_int
+    L.b3gs_background_sheet.argtypes = [V, I32, I32, V, V, F, V, V, V, V, V]
+    L.b3gs_background_sheet.restype = C.c_int
+    L.b3gs_cloud_grow_round.argtypes = [C.POINTER(B3gsCloudGrow), V]
+    L.b3gs_cloud_grow_round.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

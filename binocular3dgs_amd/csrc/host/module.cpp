@@ -50,4 +50,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_metrics(m);
   b3::bind_frames(m);
   b3::bind_gt_prep(m);
+  b3::bind_cloud(m);
 }

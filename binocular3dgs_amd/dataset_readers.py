@@ -7,8 +7,8 @@
               DTU: two fixed index lists; Blender: eight fixed train views, every 8th test frame
     extent    1.1 x the largest distance of a train camera from their mean centre (`cameras_extent`), `translate`
     points    the sparse-view rule of the reference reads keypoints_to_3d/<dataset>[_<suffix>]/<scene>_keypoints_to_3d.ply,
-              relative to the working directory: the dense matcher's cloud, which this build does not produce
-              (INTEGRATION.md section 8).  `init_points`: "matcher" (that rule), "sparse" (COLMAP's own points), or a path.
+              relative to the working directory: the dense matcher's cloud, which keypoints_to_3d.py writes from a file of
+              keypoint matches.  `init_points`: "matcher" (that rule), "sparse" (COLMAP's own points), or a path.
 
 Images are only located and measured here; read_image() decodes one to uint8 [H, W, C] at its source size (PNG with the
 stdlib reader of frames.py, anything else with Pillow when it is installed).  Nothing is resized on the host:
@@ -35,7 +35,8 @@ COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL
                  5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
                  9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
 INIT_POINTS_HELP = ('init_points is "matcher" (keypoints_to_3d/<dataset>[_<suffix>]/<scene>_keypoints_to_3d.ply under the working '
-                    'directory, the dense matcher\'s cloud), "sparse" (<source>/sparse/0/points3D.ply|.bin|.txt) or the path of a PLY file')
+                    'directory, the dense matcher\'s cloud), "sparse" (<source>/sparse/0/points3D.ply|.bin|.txt) or the path of a PLY file.  '
+                    'The matcher cloud is written by `python -m binocular3dgs_amd.keypoints_to_3d --data_path <source> --matches FILE.npz`')
 
 
 class CameraInfo(NamedTuple):

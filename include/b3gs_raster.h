@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 13
+#define B3GS_ABI_VERSION 14
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -567,6 +567,52 @@ typedef struct B3gsGtView {
 size_t b3gs_gt_workspace_bytes(int32_t nviews, const B3gsGtView* views, int32_t H, int32_t W);
 int b3gs_prepare_gt_batch(int32_t nviews, const B3gsGtView* views, int32_t H, int32_t W, int32_t white_background,
                           float dtu_threshold, void* workspace, b3gs_stream_t stream);
+
+/* ---- the matcher cloud (ABI 14; binocular3dgs_amd/matcher_cloud.py) ---------------------------
+ * What the reference's submodules/dense_matcher/triangulate.py does once the matcher has produced its keypoints: DLT
+ * triangulation with the reprojection and frame filters and the colour lookup (lines 165-219), the DTU background sheet
+ * (221-238) and one round of the photo-consistency growth loop (264-379).  All pointers are device pointers unless said
+ * otherwise; nothing reads the device.  workspace: b3gs_cloud_workspace_bytes(n) bytes, 256-byte aligned, n = matches /
+ * pixels / candidates of the call.
+ *
+ * b3gs_triangulate_matches: one view pair.  proj_ref / proj_src [3,4], intrinsic [3,3], w2c_ref / w2c_src [4,4], kp [N,2],
+ * image uint8 [H,W,3]; points [N,3] and colors [N,3] receive the kept matches densely in input order, *count their number.
+ * b3gs_background_sheet: inv_intrinsic_t = inverse(intrinsic^T) [3,3], c2w [4,4]; for every pixel whose largest channel is
+ * >= 254 the world point of `depth` (pixel order), colour 255; outputs sized H*W.
+ * b3gs_cloud_grow_round: see B3gsCloudGrow.  At most two launches (three when `init` counts the starting cloud first). */
+size_t b3gs_cloud_workspace_bytes(int64_t n);
+int b3gs_triangulate_matches(int32_t N, const float* proj_ref, const float* proj_src, const float* intrinsic,
+                             const float* w2c_ref, const float* w2c_src, const float* kp_ref, const float* kp_src,
+                             const uint8_t* image, int32_t W, int32_t H, float reproj_threshold, float* points,
+                             uint8_t* colors, int32_t* count, void* workspace, b3gs_stream_t stream);
+int b3gs_background_sheet(const uint8_t* image, int32_t W, int32_t H, const float* inv_intrinsic_t, const float* c2w,
+                          float depth, float* points, uint8_t* colors, int32_t* count, void* workspace,
+                          b3gs_stream_t stream);
+#define B3GS_CLOUD_MAX_VIEWS 16
+typedef struct B3gsCloudGrow {
+  int32_t W, H, n_views;          /* the selected views, 2..16 of them */
+  int32_t ref, src;               /* this round's two views (slots into the arrays below), ref != src */
+  int32_t n_seeds, n_samples;     /* candidates = n_seeds * n_samples, candidate (i, j) = points[seed_idx[i]] + noise[i,j] * alpha */
+  int32_t n_start;                /* length of the cloud before growth: seed indices lie below it */
+  int32_t h_patch_size;           /* 5 (an 11x11 window); anything else is refused */
+  int32_t init;                   /* non-zero: zero the grids and count points[0, n_start) into them first */
+  float fx, fy, cx, cy, alpha, ssim_threshold;
+  const uint8_t* images;          /* [n_views, H, W, 3] */
+  const float* w2c;               /* [n_views, 4, 4] */
+  const float* window;            /* [121] */
+  const int32_t* seed_idx;        /* [n_seeds] */
+  const float* noise;             /* [n_seeds, n_samples, 3] */
+  float* points;                  /* [capacity, 3] */
+  float* colors;                  /* [capacity, 3], 0..255 as float32 */
+  int32_t capacity;
+  int32_t* length;                /* device word: points in the cloud; keeps counting past `capacity` (nothing is written there) */
+  int32_t* overflow;              /* device word: set when a point did not fit, or when a grid margin was violated (bit 1) */
+  int32_t* grids;                 /* [n_views, H + 2, W + 2] points of the cloud per rounded pixel, one cell of margin */
+  void* workspace;
+  float* debug_ssim;              /* [candidates] or NULL: mean SSIM of every live candidate (0 for the others) */
+  uint8_t* debug_mask;            /* [candidates] or NULL: patch_mask */
+} B3gsCloudGrow;
+int b3gs_cloud_grow_round(const B3gsCloudGrow* io, b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
