@@ -478,6 +478,7 @@ class ViewShardedStep:
         self._row_mask = None             # bitmap of the gradients now in the slab (None = dense)
         self._pending_views = None        # views whose chain rule reduce_and_update() still has to run (data parallel)
         self.tail_events = None           # bench: list that receives the HIP events of every pipelined tail
+        self.densify_stats = True         # False: no view feeds the densification statistics (past densify_until_iter)
 
     @classmethod
     def from_global(cls, model, global_pairs, bg, rank: Optional[int] = None, world: Optional[int] = None, **kw):
@@ -705,7 +706,7 @@ class ViewShardedStep:
 
     def _render_views(self):
         if self.fused is not None:
-            return self.fused.render_batch([(v.cam, v.slot, v.role == 0) for v in self.views], self.bg)
+            return self.fused.render_batch([(v.cam, v.slot, v.role == 0 and self.densify_stats) for v in self.views], self.bg)
         return [self.render(v.cam, self.model, self.pipe, self.bg) for v in self.views]
 
     def compute_grads(self, pair_grad_fn=None, loss_fn=None, batch_loss_fn=None):

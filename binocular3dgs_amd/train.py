@@ -3,7 +3,9 @@
 The reference's train.py: a COLMAP / Blender dataset folder in, a trained model out.
 
     Scene.from_dataset     readers on the host, ground truth (and the DTU background mask) prepared on the device
-    IterationSchedule      the iteration of train.py:65-202, every statement a HIP launch of this build
+    IterationSchedule      the iteration of train.py:65-202, every statement a HIP launch of this build (--step schedule)
+    GraphTrainer           the same iteration on the fused step, one HIP-graph replay per iteration (--step graph); the draws,
+                           reports, saves and checkpoints are the same, a checkpoint of one mode resumes in the other
     per iteration          random.choice(views); past --shift_cam_start: torch.rand(1) * cam_trans_dist and a random sign
                            (train.py:92,125-126, the same draws from the same generators)
     --test_iterations      evaluate.training_report's "[ITER n] Evaluating test|train: L1 .. PSNR .." lines
@@ -73,6 +75,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--n_views", type=int, default=3)
     p.add_argument("--suffix", type=str, default=None)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--step", choices=("schedule", "graph"), default="schedule",
+                   help='"schedule": the reference-shaped loop, one launch per statement (schedule.IterationSchedule); "graph": '
+                        'the same iteration on the fused step, one HIP-graph replay per iteration (graph_trainer.GraphTrainer)')
     return p
 
 
@@ -82,7 +87,8 @@ def cfg_args_text(args) -> str:
 
 
 def run(args) -> dict:
-    """Trains; -> {"model_path", "first_iteration", "iterations", "loss" (the last total loss), "points", "reports"}."""
+    """Trains; -> {"model_path", "first_iteration", "iterations", "loss" (the last total loss), "points", "reports",
+    "captures" (graphs captured by --step graph; 0 in schedule mode)}."""
     from . import checkpoint
     from .gaussian_model import GaussianModel
     from .render import PipelineParams
@@ -122,13 +128,18 @@ def run(args) -> dict:
             say("\n[ITER {}] Saving Gaussians".format(it))
             scene.save(it)
 
-    sched = IterationSchedule(model, scene, PipelineParams(), background, iterations=args.iterations,
-                              shift_cam_start=args.shift_cam_start, binocular=args.binocular_consistency,
-                              opacity_decay_factor=args.opacity_decay_factor if args.opacity_decay else None,
-                              lambda_dssim=args.lambda_dssim, densify_from_iter=args.densify_from_iter,
-                              densify_until_iter=args.densify_until_iter, densification_interval=args.densification_interval,
-                              densify_grad_threshold=args.densify_grad_threshold, test_cameras=scene.getTestCameras(),
-                              test_iterations=args.test_iterations, after_report=after_report)
+    kw = dict(iterations=args.iterations, shift_cam_start=args.shift_cam_start, binocular=args.binocular_consistency,
+              opacity_decay_factor=args.opacity_decay_factor if args.opacity_decay else None,
+              lambda_dssim=args.lambda_dssim, densify_from_iter=args.densify_from_iter,
+              densify_until_iter=args.densify_until_iter, densification_interval=args.densification_interval,
+              densify_grad_threshold=args.densify_grad_threshold, test_cameras=scene.getTestCameras(),
+              test_iterations=args.test_iterations, after_report=after_report)
+    if getattr(args, "step", "schedule") == "graph":
+        from .graph_trainer import GraphTrainer
+        sched = GraphTrainer(model, scene, PipelineParams(), background, save_iterations=args.save_iterations,
+                             checkpoint_iterations=args.checkpoint_iterations, **kw)
+    else:
+        sched = IterationSchedule(model, scene, PipelineParams(), background, **kw)
     views = sched.views
     loss = None
     for it in range(first_iter + 1, args.iterations + 1):
@@ -142,10 +153,12 @@ def run(args) -> dict:
         if it in args.checkpoint_iterations:
             say("\n[ITER {}] Saving Checkpoint".format(it))
             checkpoint.save(args.model_path + "/chkpnt" + str(it) + ".pth", model, model.optimizer, it)
+    if hasattr(sched, "settle"):
+        sched.settle()
     say("\nTraining complete.")
     return {"model_path": args.model_path, "first_iteration": first_iter + 1, "iterations": args.iterations,
             "loss": None if loss is None else float(loss.detach()), "points": int(model.get_xyz.shape[0]), "reports": dict(sched.reports),
-            "scene": scene, "model": model}
+            "scene": scene, "model": model, "captures": getattr(sched, "captures", 0), "trainer": sched}
 
 
 def main(argv=None) -> int:
