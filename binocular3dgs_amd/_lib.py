@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("B3GS_LIB") or os.path.join(_HERE, "libb3gs_raster.so")   # B3GS_LIB: A/B builds of the kernels
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 OK = 0
 ERR_NAMES = {-1: "B3GS_ERR_ARG", -2: "B3GS_ERR_ALLOC", -3: "B3GS_ERR_HIP", -4: "B3GS_ERR_CAPACITY",
              -5: "B3GS_ERR_NO_DEVICE"}
@@ -119,6 +119,13 @@ class B3gsCloudGrow(C.Structure):
                 + [(n, C.c_void_p) for n in ("length", "overflow", "grids", "workspace", "debug_ssim", "debug_mask")])
 
 
+class B3gsSweepPair(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("W", "H", "D", "stride", "radius")]
+                + [(n, C.c_float) for n in ("near", "far", "inv_far", "step", "min_score", "margin", "min_var", "cyc_steps")]
+                + [(n, C.c_void_p) for n in ("image_a", "image_b", "homographies", "proj", "kp_source", "kp_target", "score", "count",
+                                             "node_invd", "node_score", "node_k", "workspace")])
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -144,7 +151,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # ABI 13: ground-truth preparation of dataset images
            "b3gs_gt_workspace_bytes", "b3gs_prepare_gt_batch",
            # ABI 14: the matcher cloud
-           "b3gs_cloud_workspace_bytes", "b3gs_triangulate_matches", "b3gs_background_sheet", "b3gs_cloud_grow_round")
+           "b3gs_cloud_workspace_bytes", "b3gs_triangulate_matches", "b3gs_background_sheet", "b3gs_cloud_grow_round",
+           # ABI 15: the plane-sweep stereo matcher
+           "b3gs_sweep_workspace_bytes", "b3gs_sweep_match_pair")
 
 _lib = None
 
@@ -268,6 +277,10 @@ def lib():
     L.b3gs_background_sheet.restype = C.c_int
     L.b3gs_cloud_grow_round.argtypes = [C.POINTER(B3gsCloudGrow), V]
     L.b3gs_cloud_grow_round.restype = C.c_int
+    L.b3gs_sweep_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.b3gs_sweep_workspace_bytes.restype = C.c_size_t
+    L.b3gs_sweep_match_pair.argtypes = [C.POINTER(B3gsSweepPair), V]
+    L.b3gs_sweep_match_pair.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -55,5 +55,6 @@ void bind_metrics(pybind11::module_& m);
 void bind_frames(pybind11::module_& m);
 void bind_gt_prep(pybind11::module_& m);
 void bind_cloud(pybind11::module_& m);
+void bind_sweep(pybind11::module_& m);
 
 }  // namespace b3

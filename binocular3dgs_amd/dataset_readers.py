@@ -36,7 +36,8 @@ COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL
                  9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
 INIT_POINTS_HELP = ('init_points is "matcher" (keypoints_to_3d/<dataset>[_<suffix>]/<scene>_keypoints_to_3d.ply under the working '
                     'directory, the dense matcher\'s cloud), "sparse" (<source>/sparse/0/points3D.ply|.bin|.txt) or the path of a PLY file.  '
-                    'The matcher cloud is written by `python -m binocular3dgs_amd.keypoints_to_3d --data_path <source> --matches FILE.npz`')
+                    'The matcher cloud is written by `python -m binocular3dgs_amd.keypoints_to_3d --data_path <source> --matches FILE.npz`, '
+                    'or without a match file by `... --data_path <source> --matcher sweep` (the plane-sweep matcher, not the reference\'s network)')
 
 
 class CameraInfo(NamedTuple):

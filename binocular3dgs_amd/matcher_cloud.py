@@ -10,7 +10,8 @@ its dense matcher has produced `kp_source` / `kp_target` for a view pair (INTEGR
     write_cloud_ply    x y z float, red green blue uchar, binary little endian
 
 All three hot paths are HIP kernels (csrc/cloud.hip) behind `_C`; there is no CPU path.  The matcher network itself is not
-part of this build: matches come from a file.
+part of this build: matches come from a file, or from the plane-sweep matcher of sweep_matcher.py (`matcher="sweep"`), which
+is a classical stand-in and not the reference's network.
 
 Matches file: a plain .npz with, for every ordered pair (ref, src) of selected views that has matches, two float32 [N, 2]
 arrays of pixel coordinates (x, y) AT THE WORKING RESOLUTION (the image size divided by `resolution`):
@@ -378,14 +379,32 @@ def load_images(views: DatasetViews, resolution: int, device) -> List[torch.Tens
     return out
 
 
-def build_cloud(source_path: str, matches, *, dataset_name: str = "LLFF", n_views: int = 3, resolution: int = 4,
-                dtu_sparse_indices: Sequence[int] = DTU_SPARSE_INDICES, device="cuda", **grow) -> Tuple[np.ndarray, np.ndarray]:
-    """-> (xyz float32 [P,3], rgb uint8 [P,3]) of a dataset folder and its matches (a file or a mapping, see the module's
-    docstring).  `grow`: keyword arguments of grow_cloud (LLFF only)."""
-    matches = load_matches(matches)
+def build_cloud(source_path: str, matches=None, *, dataset_name: str = "LLFF", n_views: int = 3, resolution: int = 4,
+                dtu_sparse_indices: Sequence[int] = DTU_SPARSE_INDICES, device="cuda", matcher: str = "file", sweep=None,
+                save_matches: Optional[str] = None, **grow) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (xyz float32 [P,3], rgb uint8 [P,3]) of a dataset folder and its matches.  matcher="file": `matches` is a file or a
+    mapping (see the module's docstring).  matcher="sweep": the matches come from the plane-sweep matcher (sweep_matcher.py,
+    `sweep`: its SweepParams) on the images loaded here, and are also written to `save_matches` when that is given.
+    `grow`: keyword arguments of grow_cloud (LLFF only)."""
+    if matcher not in ("file", "sweep"):
+        raise ValueError(f'matcher is "file" or "sweep", not {matcher!r}')
+    if matcher == "file":
+        if matches is None:
+            raise ValueError('matcher="file" needs the matches (a file or a mapping)')
+        matches = load_matches(matches)
+    elif matches is not None:
+        raise ValueError('matcher="sweep" computes the matches itself: give no `matches`')
     views = read_views(source_path, resolution)
     ref_indices = select_views(len(views.names), dataset_name, n_views, dtu_sparse_indices)
     images = load_images(views, resolution, device)
+    if matcher == "sweep":
+        from . import sweep_matcher as sm
+        params = sweep if sweep is not None else sm.SweepParams()
+        near, far = sm.resolve_range(source_path, views, ref_indices, params)
+        found = sm.match_images(views, images, ref_indices, near, far, params)
+        if save_matches:
+            sm.write_matches(save_matches, found)
+        matches = load_matches(found)
     k0 = views.intrinsics[0]
     pts, cols = [], []
     plan = plan_pairs(views, ref_indices)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 14
+#define B3GS_ABI_VERSION 15
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -613,6 +613,35 @@ typedef struct B3gsCloudGrow {
   uint8_t* debug_mask;            /* [candidates] or NULL: patch_mask */
 } B3gsCloudGrow;
 int b3gs_cloud_grow_round(const B3gsCloudGrow* io, b3gs_stream_t stream);
+
+/* ---- the plane-sweep stereo matcher (ABI 15; binocular3dgs_amd/sweep_matcher.py) ---------------
+ * Keypoint matches of one calibrated view pair {a, b}, both directions in one call, without a network: per node of the
+ * reference view (pixels 3 + i stride, row-major) the best of D fronto-parallel inverse-depth hypotheses by the ZNCC of the
+ * 7x7 gray patches, a uniqueness test, a parabola refinement, a left/right check against the other direction's node map and
+ * an ordered compaction.  Five launches; nothing reads the device, nothing synchronises.  Direction 0 is a -> b, 1 is b -> a.
+ * nodes = ((W - 7) / stride + 1) * ((H - 7) / stride + 1); every output holds `nodes` rows per direction, so nothing overflows.
+ * workspace: b3gs_sweep_workspace_bytes(W, H, D, stride) bytes (0: bad sizes), 256-byte aligned. */
+typedef struct B3gsSweepPair {
+  int32_t W, H, D, stride;
+  int32_t radius;                 /* 3 (a 7x7 patch); anything else is refused */
+  float near, far;                /* 0 < near < far: the depth range the hypotheses span */
+  float inv_far, step;            /* invd[k] = inv_far + step * k, as float32 of the float64 values */
+  float min_score, margin, min_var, cyc_steps;
+  const uint8_t* image_a;         /* [H, W, 3] */
+  const uint8_t* image_b;
+  const float* homographies;      /* [2, D, 3, 3]: pixel of the direction's reference view -> pixel of the other view, plane k */
+  const float* proj;              /* [2, 12]: K R K^-1 (9, row-major) and K t (3) of the direction: q ~ M p + (K t) invd */
+  float* kp_source;               /* [2, nodes, 2] the kept nodes (x, y), in node order */
+  float* kp_target;               /* [2, nodes, 2] their correspondences in the other view */
+  float* score;                   /* [2, nodes]    their ZNCC */
+  int32_t* count;                 /* [2] device words: kept matches per direction */
+  float* node_invd;               /* [2, nodes] the node map: refined inverse depth, -1 = none */
+  float* node_score;              /* [2, nodes] best valid score (0: no valid hypothesis) */
+  int32_t* node_k;                /* [2, nodes] best valid hypothesis (-1: none) */
+  void* workspace;
+} B3gsSweepPair;
+size_t b3gs_sweep_workspace_bytes(int32_t W, int32_t H, int32_t D, int32_t stride);
+int b3gs_sweep_match_pair(const B3gsSweepPair* io, b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
