@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("B3GS_LIB") or os.path.join(_HERE, "libb3gs_raster.so")   # B3GS_LIB: A/B builds of the kernels
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 OK = 0
 ERR_NAMES = {-1: "B3GS_ERR_ARG", -2: "B3GS_ERR_ALLOC", -3: "B3GS_ERR_HIP", -4: "B3GS_ERR_CAPACITY",
              -5: "B3GS_ERR_NO_DEVICE"}
@@ -153,7 +153,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # ABI 14: the matcher cloud
            "b3gs_cloud_workspace_bytes", "b3gs_triangulate_matches", "b3gs_background_sheet", "b3gs_cloud_grow_round",
            # ABI 15: the plane-sweep stereo matcher
-           "b3gs_sweep_workspace_bytes", "b3gs_sweep_match_pair")
+           "b3gs_sweep_workspace_bytes", "b3gs_sweep_match_pair",
+           # ABI 16: baseline JPEG of rendered frames
+           "b3gs_jpeg_workspace_bytes", "b3gs_jpeg_encode_batch")
 
 _lib = None
 
@@ -281,6 +283,10 @@ def lib():
     L.b3gs_sweep_workspace_bytes.restype = C.c_size_t
     L.b3gs_sweep_match_pair.argtypes = [C.POINTER(B3gsSweepPair), V]
     L.b3gs_sweep_match_pair.restype = C.c_int
+    L.b3gs_jpeg_workspace_bytes.argtypes = [I32, I32, I32]
+    L.b3gs_jpeg_workspace_bytes.restype = C.c_size_t
+    L.b3gs_jpeg_encode_batch.argtypes = [I32, C.POINTER(C.c_void_p), I32, I32, V, V, I64, V, V, V]
+    L.b3gs_jpeg_encode_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

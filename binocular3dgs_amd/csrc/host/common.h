@@ -56,5 +56,6 @@ void bind_frames(pybind11::module_& m);
 void bind_gt_prep(pybind11::module_& m);
 void bind_cloud(pybind11::module_& m);
 void bind_sweep(pybind11::module_& m);
+void bind_jpeg(pybind11::module_& m);
 
 }  // namespace b3

@@ -1,9 +1,12 @@
 """python -m binocular3dgs_amd.spiral -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--resolution R] [--white_background]
+                                      [--video] [--no_png] [--fps 25] [--quality 90]
 
 The reference's spiral.py: the trained point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply, rendered along the
 180-frame spiral of <source_path>/poses_bounds.npy (DTU when the source path contains 'scan'), written as %05d.png,
 depth_%05d.png and cdepth_%05d.png to <model_path>/render/ours_<it>/.  Renders and frame encoding run in batches on the
-device (frames.render_path); video encoding is left to the user (the ffmpeg lines are printed).
+device (frames.render_path).  --video also encodes the three streams as baseline JPEG on the device and writes
+<model_path>/out_<scene>.avi, out_depth_<scene>.avi and out_cdepth_<scene>.avi (Motion-JPEG in AVI; the reference makes H.264
+MP4 files of these names with ffmpeg); --no_png then skips the PNG files.  Without --video the ffmpeg lines are printed.
 
 Defaults for source_path, sh_degree, resolution and white_background come from <model_path>/cfg_args when it exists (the
 Namespace(...) line train.py writes, read with `ast`: literals only, nothing is executed); the command line wins.
@@ -51,7 +54,7 @@ def max_iteration(model_path: str) -> int:
 
 
 def run(model_path: str, source_path: str = None, iteration: int = -1, resolution=None, white_background=None,
-        sh_degree=None, n_frames: int = 180) -> str:
+        sh_degree=None, n_frames: int = 180, video: bool = False, png: bool = True, fps: float = 25.0, quality: int = 90) -> str:
     from . import camera_path, frames
     from .gaussian_model import GaussianModel
     cfg = read_cfg_args(model_path)
@@ -67,11 +70,20 @@ def run(model_path: str, source_path: str = None, iteration: int = -1, resolutio
     cams = camera_path.spiral_cameras_from_dir(source_path, n_frames=n_frames, resolution=resolution, device="cuda")
     bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
     out_dir = os.path.join(model_path, "render", "ours_{}".format(it))
+    scene = os.path.basename(os.path.normpath(source_path))
     t0 = time.perf_counter()
+    if video:
+        res = frames.render_path(model, cams, bg, out_dir, video=(model_path, scene), png=png, fps=fps, quality=quality)
+        dt = time.perf_counter() - t0
+        where = out_dir if png else "no PNG files"
+        print(f"{len(cams)} frames ({cams[0].image_width}x{cams[0].image_height}) -> {where} in {dt:.2f} s")
+        print(f"video (Motion-JPEG AVI, {fps:g} fps, quality {quality}):")
+        for path in res["video"]:
+            print(f"  {path}")
+        return out_dir
     frames.render_path(model, cams, bg, out_dir)
     dt = time.perf_counter() - t0
     print(f"{len(cams)} frames ({cams[0].image_width}x{cams[0].image_height}) -> {out_dir} in {dt:.2f} s")
-    scene = os.path.basename(os.path.normpath(source_path))
     print("video (not encoded here):")
     for pat, out in (("%05d.png", "out_{}.mp4"), ("depth_%05d.png", "out_depth_{}.mp4"), ("cdepth_%05d.png", "out_cdepth_{}.mp4")):
         print(f"  ffmpeg -i {os.path.join(out_dir, pat)} -q 2 {os.path.join(model_path, out.format(scene))} -y")
@@ -87,8 +99,15 @@ def main(argv=None) -> int:
     p.add_argument("-w", "--white_background", action="store_true", default=None)
     p.add_argument("--sh_degree", type=int, default=None)
     p.add_argument("--frames", type=int, default=180, help="frames of the spiral (the reference: 180)")
+    p.add_argument("--video", action="store_true", help="also write out_<scene>.avi, out_depth_<scene>.avi, out_cdepth_<scene>.avi")
+    p.add_argument("--no_png", action="store_true", help="with --video: write no PNG files")
+    p.add_argument("--fps", type=float, default=25.0, help="frame rate of the videos (ffmpeg's default for an image sequence)")
+    p.add_argument("--quality", type=int, default=90, help="JPEG quality of the video frames, 1..100")
     a = p.parse_args(argv)
-    run(a.model_path, a.source_path, a.iteration, a.resolution, a.white_background, a.sh_degree, a.frames)
+    if a.no_png and not a.video:
+        p.error("--no_png needs --video")
+    run(a.model_path, a.source_path, a.iteration, a.resolution, a.white_background, a.sh_degree, a.frames,
+        video=a.video, png=not a.no_png, fps=a.fps, quality=a.quality)
     return 0
 
 

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 15
+#define B3GS_ABI_VERSION 16
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -642,6 +642,26 @@ typedef struct B3gsSweepPair {
 } B3gsSweepPair;
 size_t b3gs_sweep_workspace_bytes(int32_t W, int32_t H, int32_t D, int32_t stride);
 int b3gs_sweep_match_pair(const B3gsSweepPair* io, b3gs_stream_t stream);
+
+/* ---- baseline JPEG of rendered frames (ABI 16; binocular3dgs_amd/frames.py) ---------------------
+ * The entropy-coded scan of a baseline sequential JPEG of up to B3GS_MAX_FRAME_VIEWS uint8 [H,W,3] images of one W x H (what
+ * the frame encoder of ABI 12 writes): YCbCr 4:2:0, 8 bit, one interleaved scan (Y00 Y01 Y10 Y11 Cb Cr per 16 x 16 MCU, MCUs
+ * row by row), the Annex K "typical" Huffman tables, no restart markers, 0xFF stuffed with 0x00, the last byte filled with
+ * 1-bits.  Header (SOI .. SOS) and EOI are the same for every frame of a (W, H, tables): the caller puts them around the scan.
+ * Integer arithmetic throughout (tests/jpeg_ref.py restates it; the bytes agree):
+ *   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16,
+ *   Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16; edges replicated to whole MCUs; chroma = (sum of 2 x 2 + bias) >> 2 with
+ *   bias 1, 2, 1, 2, .. along a row; the 13-bit Loeffler-Ligtenberg-Moschytz DCT of sample - 128 (rows, then columns, scaled
+ *   by 8); coefficient = sign(c) * ((|c| + 4 q) / (8 q)).
+ * images: HOST array of nviews device pointers.  qtables: device uint16[128], the luminance then the chrominance table,
+ * row-major, entries 1..255.  Frame i goes to out + i * capacity and its byte count to lengths[i] (device); a frame whose scan
+ * is longer than `capacity` is not written at all (no byte of `out` changes for it) and reports -1: the bound is about 10
+ * bytes per pixel.  Six launches whatever nviews; nothing reads the device, nothing synchronises; capturable in a graph.
+ * 1 <= nviews <= 8, 1 <= W, H <= 65535, capacity >= 1.
+ * workspace: b3gs_jpeg_workspace_bytes(nviews, H, W) bytes (0: bad sizes), 256-byte aligned, no initial content needed. */
+size_t b3gs_jpeg_workspace_bytes(int32_t nviews, int32_t H, int32_t W);
+int b3gs_jpeg_encode_batch(int32_t nviews, const uint8_t* const* images, int32_t H, int32_t W, const uint16_t* qtables,
+                           uint8_t* out, int64_t capacity, int64_t* lengths, void* workspace, b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
