@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("B3GS_LIB") or os.path.join(_HERE, "libb3gs_raster.so")   # B3GS_LIB: A/B builds of the kernels
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 OK = 0
 ERR_NAMES = {-1: "B3GS_ERR_ARG", -2: "B3GS_ERR_ALLOC", -3: "B3GS_ERR_HIP", -4: "B3GS_ERR_CAPACITY",
              -5: "B3GS_ERR_NO_DEVICE"}
@@ -126,6 +126,16 @@ class B3gsSweepPair(C.Structure):
                                              "node_invd", "node_score", "node_k", "workspace")])
 
 
+class B3gsTsdfVolume(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3), ("voxel", C.c_float),
+                ("tsdf", C.c_void_p), ("weight", C.c_void_p), ("rgb", C.c_void_p)]
+
+
+class B3gsTsdfView(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("alpha", C.c_void_p), ("colour", C.c_void_p), ("rot", C.c_float * 9),
+                ("trans", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -155,7 +165,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # ABI 15: the plane-sweep stereo matcher
            "b3gs_sweep_workspace_bytes", "b3gs_sweep_match_pair",
            # ABI 16: baseline JPEG of rendered frames
-           "b3gs_jpeg_workspace_bytes", "b3gs_jpeg_encode_batch")
+           "b3gs_jpeg_workspace_bytes", "b3gs_jpeg_encode_batch",
+           # ABI 17: TSDF fusion and marching tetrahedra
+           "b3gs_tsdf_integrate_batch", "b3gs_mesh_workspace_bytes", "b3gs_mesh_count", "b3gs_mesh_emit")
 
 _lib = None
 
@@ -287,6 +299,14 @@ def lib():
     L.b3gs_jpeg_workspace_bytes.restype = C.c_size_t
     L.b3gs_jpeg_encode_batch.argtypes = [I32, C.POINTER(C.c_void_p), I32, I32, V, V, I64, V, V, V]
     L.b3gs_jpeg_encode_batch.restype = C.c_int
+    L.b3gs_tsdf_integrate_batch.argtypes = [C.POINTER(B3gsTsdfVolume), I32, C.POINTER(B3gsTsdfView), I32, I32, F, F, F, V]
+    L.b3gs_tsdf_integrate_batch.restype = C.c_int
+    L.b3gs_mesh_workspace_bytes.argtypes = [I32, I32, I32]
+    L.b3gs_mesh_workspace_bytes.restype = C.c_size_t
+    L.b3gs_mesh_count.argtypes = [C.POINTER(B3gsTsdfVolume), F, V, V]
+    L.b3gs_mesh_count.restype = C.c_int
+    L.b3gs_mesh_emit.argtypes = [C.POINTER(B3gsTsdfVolume), V, I64, I64, V, V, V, V]
+    L.b3gs_mesh_emit.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -57,5 +57,6 @@ void bind_gt_prep(pybind11::module_& m);
 void bind_cloud(pybind11::module_& m);
 void bind_sweep(pybind11::module_& m);
 void bind_jpeg(pybind11::module_& m);
+void bind_mesh(pybind11::module_& m);
 
 }  // namespace b3

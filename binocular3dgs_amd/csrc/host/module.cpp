@@ -53,4 +53,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_cloud(m);
   b3::bind_sweep(m);
   b3::bind_jpeg(m);
+  b3::bind_mesh(m);
 }

@@ -1,0 +1,112 @@
+"""python -m binocular3dgs_amd.extract_mesh -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--views train|test|all]
+                                            [--resolution 256 | --voxel_size S] [--truncation_voxels 4] [--alpha_min 0.5]
+                                            [--min_weight 1] [--bounds x0 y0 z0 x1 y1 z1]
+
+A triangle mesh of a trained model: the point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply is rendered from
+the chosen cameras, depth, alpha and colour are fused into a TSDF volume and the zero level set is extracted, all on the
+device (mesh.fuse_model).  Writes <model_path>/mesh/iteration_<it>/mesh.ply (binary PLY, coloured vertices) and prints the
+voxel, vertex and triangle counts.
+
+The model and the cameras are found the way spiral.py finds them: source path, images folder, image resolution, background,
+SH degree, dataset name and view count come from <model_path>/cfg_args; the command line wins.  A model folder whose dataset
+is not at hand still works with --views all: the cameras are then those of <model_path>/cameras.json, at the size it records.
+--resolution is the number of voxels along the longest axis of the bounds (NOT the image resolution, which is cfg_args').
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="extract a triangle mesh from a trained model (TSDF fusion of rendered depth)")
+    p.add_argument("-m", "--model_path", required=True)
+    p.add_argument("-s", "--source_path", default=None)
+    p.add_argument("--iteration", type=int, default=-1)
+    p.add_argument("--views", choices=("train", "test", "all"), default="train")
+    size = p.add_mutually_exclusive_group()
+    size.add_argument("--resolution", type=int, default=None, help="voxels along the longest axis of the bounds (default 256)")
+    size.add_argument("--voxel_size", type=float, default=None)
+    p.add_argument("--truncation_voxels", type=float, default=4.0)
+    p.add_argument("--alpha_min", type=float, default=0.5)
+    p.add_argument("--min_weight", type=float, default=1.0)
+    p.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    return p
+
+
+def cameras_from_json(path: str, device="cuda"):
+    """The cameras of a cameras.json (dataset_readers.camera_json / the reference's camera_to_JSON), without images."""
+    from .camera import Camera, focal2fov
+    with open(path) as fp:
+        entries = json.load(fp)
+    cams = []
+    for e in entries:
+        R = np.asarray(e["rotation"], dtype=np.float64)                 # camera -> world
+        T = -R.T @ np.asarray(e["position"], dtype=np.float64)          # world -> camera translation
+        W, H = int(e["width"]), int(e["height"])
+        cams.append(Camera(R, T, focal2fov(e["fx"], W), focal2fov(e["fy"], H), W, H, uid=int(e["id"]), device=device,
+                           image_name=e.get("img_name")))
+    return cams
+
+
+def load_cameras(model_path: str, cfg: dict, source_path, views: str, device="cuda"):
+    source_path = source_path or cfg.get("source_path")
+    if source_path and os.path.isdir(source_path):
+        from .scene import Scene
+        scene = Scene.from_dataset(source_path, None, images=cfg.get("images", "images"), eval=bool(cfg.get("eval", False)),
+                                   n_views=int(cfg.get("n_views", 3)), dataset_name=cfg.get("dataset_name", "LLFF"),
+                                   suffix=cfg.get("suffix"), resolution=cfg.get("resolution", -1),
+                                   white_background=bool(cfg.get("white_background", False)),
+                                   init_points=cfg.get("init_points", "matcher"), shuffle=False, device=device)
+        train, test = scene.getTrainCameras(), scene.getTestCameras()
+        return {"train": train, "test": test, "all": train + test}[views]
+    path = os.path.join(model_path, "cameras.json")
+    if views != "all" or not os.path.exists(path):
+        raise ValueError("no dataset folder: pass -s, or use --views all next to the model's cameras.json")
+    return cameras_from_json(path, device)
+
+
+def run(model_path: str, source_path=None, iteration: int = -1, views: str = "train", resolution=None, voxel_size=None,
+        truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, bounds=None) -> str:
+    from . import mesh
+    from .gaussian_model import GaussianModel
+    from .spiral import max_iteration, read_cfg_args
+    cfg = read_cfg_args(model_path)
+    it = max_iteration(model_path) if iteration == -1 else iteration
+    model = GaussianModel(int(cfg.get("sh_degree", 1)))
+    model.load_ply(os.path.join(model_path, "point_cloud", "iteration_" + str(it), "point_cloud.ply"))
+    cams = load_cameras(model_path, cfg, source_path, views)
+    if not cams:
+        raise ValueError(f"no {views} cameras")
+    white = bool(cfg.get("white_background", False))
+    bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
+    t0 = time.perf_counter()
+    vertices, colours, faces, vol = mesh.fuse_model(
+        model, cams, bg, resolution=resolution, voxel_size=voxel_size, bounds=None if bounds is None else (bounds[:3], bounds[3:]),
+        truncation_voxels=truncation_voxels, alpha_min=alpha_min, min_weight=min_weight, return_volume=True)
+    out_dir = os.path.join(model_path, "mesh", "iteration_{}".format(it))
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, "mesh.ply")
+    mesh.write_mesh_ply(out, vertices, colours, faces)
+    dt = time.perf_counter() - t0
+    nx, ny, nz = vol.dims
+    print(f"{len(cams)} views -> {nx} x {ny} x {nz} voxels of {vol.voxel_size:g}: {vertices.shape[0]} vertices, "
+          f"{faces.shape[0]} triangles -> {out} in {dt:.2f} s")
+    return out
+
+
+def main(argv=None) -> int:
+    a = parser().parse_args(argv)
+    run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
+        a.min_weight, a.bounds)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

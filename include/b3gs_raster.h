@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 16
+#define B3GS_ABI_VERSION 17
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -662,6 +662,68 @@ int b3gs_sweep_match_pair(const B3gsSweepPair* io, b3gs_stream_t stream);
 size_t b3gs_jpeg_workspace_bytes(int32_t nviews, int32_t H, int32_t W);
 int b3gs_jpeg_encode_batch(int32_t nviews, const uint8_t* const* images, int32_t H, int32_t W, const uint16_t* qtables,
                            uint8_t* out, int64_t capacity, int64_t* lengths, void* workspace, b3gs_stream_t stream);
+
+/* ---- a triangle mesh of a trained scene (ABI 17; binocular3dgs_amd/mesh.py) ---------------------
+ * TSDF fusion of rendered depth into a voxel volume, and marching tetrahedra over it.  tests/mesh_ref.py restates every
+ * statement in numpy float32; the volume, the vertices and the faces agree bit for bit.
+ *
+ * The volume: nx x ny x nz voxels, x fastest; the centre of voxel (i, j, k) is origin + (i + 0.5, j + 0.5, k + 0.5) * voxel.
+ * Per voxel tsdf (float32, in units of the truncation, <= 1), weight (float32, the number of views that reached it) and
+ * rgb (3 x float32, interleaved).  1 <= nx, ny, nz <= B3GS_MAX_TSDF_DIM.
+ *
+ * b3gs_tsdf_integrate_batch: 1..B3GS_MAX_TSDF_VIEWS views of one W x H (W * H <= 2^30).  One thread owns one voxel and walks
+ * the views in index order (no atomics: the result does not depend on scheduling).  Per view, one correctly rounded float32
+ * operation per statement:
+ *   c = (rot[3r] * px + rot[3r + 1] * py) + rot[3r + 2] * pz + trans[r]        the centre in the camera (r = 0, 1, 2)
+ *   skipped unless c.z > near
+ *   u = fx * (c.x / c.z) + (0.5 W - 0.5), v likewise with fy and H             the project's pixel of a point (preprocess.hip:
+ *   pixel = (rint(u), rint(v)), skipped outside the image                      ((ndc + 1) S - 1) / 2: centres at integers)
+ *   skipped unless alpha[pixel] >= alpha_min;  d = depth[pixel] / alpha[pixel]
+ *       (the renderer's depth is the alpha-weighted sum of the camera-space z of the Gaussians blended into the pixel --
+ *        render.hip accumulates record.depth * alpha * T, and preprocess.hip stores the view-space z there -- so depth / alpha
+ *        is their mean z: the same axis as c.z, no ray-length conversion)
+ *   sdf = d - c.z, skipped unless sdf >= -truncation;  val = min(1, sdf / truncation)
+ *   tsdf = (tsdf * w + val) / (w + 1), the three colour channels likewise, then w = w + 1
+ * truncation > 0, near >= 0, alpha_min > 0, voxel > 0.
+ *
+ * b3gs_mesh_count / b3gs_mesh_emit: marching tetrahedra.  Every cell (the cube between 8 voxel centres) is cut into the six
+ * tetrahedra around its diagonal (0,0,0)-(1,1,1): for the axis permutation (a, b, c), in lexicographic order, the corners
+ * 0, e_a, e_a + e_b, (1,1,1).  A cell is valid when its 8 corners have weight >= min_weight; a corner is inside when
+ * tsdf < 0 (exactly 0 is outside; zero-area triangles that follow are kept).  A vertex lives on one of the 7 edges its
+ * lower-index end owns -- slots x, y, z, xy, xz, yz, xyz -- and exists exactly when the edge changes sign and lies in a valid
+ * cell.  Vertex ids are the exclusive scan of the existing slots in (voxel linear index, slot) order, triangles come in (cell
+ * linear index, tetrahedron, table) order: one fixed output whatever the launch geometry.  position = p0 + t (p1 - p0),
+ * t = d0 / (d0 - d1), p0 the lower-index end; colour = uint8(rint(min(max((c0 + t (c1 - c0)) * 255, 0), 255))).  Triangles
+ * are wound so that the normal points to the positive (free-space) side.
+ * count writes the per-voxel slot masks and per-cell triangle counts, their block sums and, at the START of the workspace,
+ * two int64 totals {vertices, triangles}: the only words the host reads.  emit(nverts, ntris) then fills vertices
+ * [nverts, 3], colours [nverts, 3] and faces [ntris, 3]; totals beyond INT32_MAX are B3GS_ERR_ARG, and no write goes past the
+ * counts it was given.  Nothing synchronises; both are capturable in a graph.
+ * workspace: b3gs_mesh_workspace_bytes(nx, ny, nz) bytes (0: bad sizes; 6 bytes per voxel), 256-byte aligned. */
+#define B3GS_MAX_TSDF_VIEWS 8
+#define B3GS_MAX_TSDF_DIM 1024
+typedef struct B3gsTsdfVolume {
+  int32_t nx, ny, nz;
+  float origin[3];
+  float voxel;
+  float* tsdf;                    /* [nz, ny, nx] */
+  float* weight;                  /* [nz, ny, nx] */
+  float* rgb;                     /* [nz, ny, nx, 3] */
+} B3gsTsdfVolume;
+typedef struct B3gsTsdfView {
+  const float* depth;             /* [H, W] the renderer's depth */
+  const float* alpha;             /* [H, W] */
+  const float* colour;            /* [3, H, W] */
+  float rot[9];                   /* world -> camera rotation, row-major */
+  float trans[3];                 /* world -> camera translation */
+  float fx, fy;                   /* focal lengths in pixels */
+} B3gsTsdfView;
+int b3gs_tsdf_integrate_batch(const B3gsTsdfVolume* volume, int32_t nviews, const B3gsTsdfView* views, int32_t W, int32_t H,
+                              float truncation, float near, float alpha_min, b3gs_stream_t stream);
+size_t b3gs_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int b3gs_mesh_count(const B3gsTsdfVolume* volume, float min_weight, void* workspace, b3gs_stream_t stream);
+int b3gs_mesh_emit(const B3gsTsdfVolume* volume, void* workspace, int64_t nverts, int64_t ntris, float* vertices,
+                   uint8_t* colours, int32_t* faces, b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
