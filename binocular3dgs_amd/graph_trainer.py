@@ -48,6 +48,7 @@ reference's tuple: a checkpoint of either mode resumes in the other.
 from __future__ import annotations
 
 import collections
+import gc
 
 import torch
 
@@ -181,8 +182,19 @@ class FusedBackend:
             st.step(loss_fn=self._loss_fn)
         torch.cuda.current_stream(dev).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            st.step(loss_fn=self._loss_fn)
+        # The cyclic collector runs before the capture and stays out of it: a finaliser it ran there could make a call a
+        # capture forbids.  The destructor of a torch CUDAGraph is one (on ROCm it synchronises the device, and its check
+        # throws from the destructor: the process aborts), so a dropped trainer that sat in a reference cycle with its kept
+        # graphs would end this one's capture wherever the collector happened to start.
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph):
+                st.step(loss_fn=self._loss_fn)
+        finally:
+            if collecting:
+                gc.enable()
         with torch.no_grad():
             for t, s in zip(self._state(), snap):
                 t.copy_(s)

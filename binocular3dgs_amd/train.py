@@ -122,7 +122,9 @@ def run(args) -> dict:
     background = torch.tensor([1, 1, 1] if args.white_background else [0, 0, 0], dtype=torch.float32, device=dev)
 
     def after_report(it):
-        for name, (l1, psnr) in sched.reports.get(it, {}).items():
+        # (`reports`, not the trainer: a closure that named its trainer would tie the two into a reference cycle, and the
+        # trainer's kept graphs would then be destroyed wherever the cyclic collector ran, e.g. inside a later capture)
+        for name, (l1, psnr) in reports.get(it, {}).items():
             say("\n[ITER {}] Evaluating {}: L1 {} PSNR {}".format(it, name, l1, psnr))
         if it in args.save_iterations:
             say("\n[ITER {}] Saving Gaussians".format(it))
@@ -140,6 +142,7 @@ def run(args) -> dict:
                              checkpoint_iterations=args.checkpoint_iterations, **kw)
     else:
         sched = IterationSchedule(model, scene, PipelineParams(), background, **kw)
+    reports = sched.reports
     views = sched.views
     loss = None
     for it in range(first_iter + 1, args.iterations + 1):

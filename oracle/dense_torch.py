@@ -57,10 +57,20 @@ def _cov3d(scales, mod, q):
     return L @ L.transpose(1, 2)
 
 
+def _const(t):
+    """A value the published algorithm treats as a constant in its backward (the clamped view-space x/y)."""
+    return t.detach()
+
+
+def _clamp_rgb(v):
+    """Colours are clamped at 0; a clamped channel passes no gradient."""
+    return torch.clamp_min(v, 0.0)
+
+
 def render_dense(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, tanfovx, tanfovy, sh_degree=0,
                  shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                  scale_modifier=1.0, rect=None, pix_offset=None, dtype=torch.float64):
-    """Returns dict(color[3,H,W], depth[1,H,W], alpha[1,H,W], radii[P], pix[P,2]).
+    """Returns dict(color[3,H,W], depth[1,H,W], alpha[1,H,W], radii[P], pix[P,2], final_T[H,W], margin[H,W]).
 
     `rect` (optional int tensor [P,4], x0,y0,x1,y1 in tiles; all-zero rows = culled) lets the caller
     impose the integer culling decisions of another implementation so that only the differentiable
@@ -95,8 +105,8 @@ def render_dense(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H
     tz = pv[:, 2]
     txtz, tytz = pv[:, 0] / tz, pv[:, 1] / tz
     cx, cy = (txtz < -limx) | (txtz > limx), (tytz < -limy) | (tytz > limy)
-    tx = torch.where(cx, (txtz.clamp(-limx, limx) * tz).detach(), pv[:, 0])
-    ty = torch.where(cy, (tytz.clamp(-limy, limy) * tz).detach(), pv[:, 1])
+    tx = torch.where(cx, _const(txtz.clamp(-limx, limx) * tz), pv[:, 0])
+    ty = torch.where(cy, _const(tytz.clamp(-limy, limy) * tz), pv[:, 1])
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -(fx * tx) / (tz * tz), zero, fy / tz, -(fy * ty) / (tz * tz)], 1).reshape(-1, 2, 3)
     Wr = V[:3, :3].t()   # conventional W2C rotation
@@ -125,7 +135,7 @@ def render_dense(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H
     else:
         d = means3D - campos
         d = d / d.norm(dim=1, keepdim=True)
-        rgb = torch.clamp_min(_sh_rgb(sh_degree, shs, d) + 0.5, 0.0)
+        rgb = _clamp_rgb(_sh_rgb(sh_degree, shs, d) + 0.5)
 
     # (depth, index) order of the visible set.  The depth key is the FLOAT32 view depth, as in the
     # tile sort (ties in float32 must stay ties here).
@@ -160,6 +170,11 @@ def render_dense(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H
     one_m = 1 - alpha
     Tincl = torch.cumprod(one_m, dim=0)
     stop = (Tincl.detach() < 1e-4) & keep
+    # how close each pixel comes to taking another decision: the smallest relative distance of an alpha from 1/255
+    # and of a running transmittance from 1e-4.  A float32 implementation may decide otherwise below ~1e-4.
+    inf = torch.full_like(power, float("inf")).detach()
+    margin = torch.minimum(torch.where(in_rect, (a_raw.detach() * 255.0 - 1.0).abs(), inf).min(0).values,
+                           torch.where(keep, (Tincl.detach() * 1e4 - 1.0).abs(), inf).min(0).values)
     stopped = torch.cumsum(stop.to(torch.int32), dim=0) > 0
     alpha = torch.where(stopped, torch.zeros_like(alpha), alpha)
     one_m = 1 - alpha
@@ -170,4 +185,4 @@ def render_dense(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H
     dep = (wgt * depth[order].reshape(n, 1, 1)).sum(0, keepdim=True)
     alp = wgt.sum(0, keepdim=True)
     return dict(color=color, depth=dep, alpha=alp, radii=(radius * visible).to(torch.int32), pix=pix,
-                final_T=Tincl[-1])
+                final_T=Tincl[-1], margin=margin)

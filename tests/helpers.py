@@ -32,6 +32,177 @@ def small_scene(P=400, W=64, H=48, seed=0, K=4, sh_degree=1, fovx_deg=60.0, yaw=
     return d, cam
 
 
+SH_C0 = 0.28209479177387814
+
+# Per-row gradient criterion (row_err / row_failures below).  The bound is NOT taken from the kernels: it is 10x the
+# largest 99th percentile of row_err between render_dense(dtype=float32) and render_dense(dtype=float64) -- the
+# reference against itself, the float64 run's rects and robust pixel gradients (FRAGILE_MARGIN) given to both -- over the
+# six gradient tensors, every configuration the tests use (edge_scene seeds 0 and 1; (K, degree) = (16,0), (16,1), (16,2),
+# (16,3), (9,2) at scale_modifier 0.8; the two-camera placement at modifier 1, degrees 2 and 3, per camera).  The factor 10
+# leaves room for fp32 atomics in another order and an exp2-based exp.  Measured (99th percentile / maximum of row_err
+# over the touched rows), (K, degree) = (16, 3):
+#                seed 0 (713 touched)     seed 1 (725 touched)
+#   means3D      8.9e-6 / 4.1e-5          1.1e-5 / 7.7e-5
+#   opacities    7.7e-6 / 1.7e-5          1.1e-5 / 3.1e-5
+#   scales       9.7e-6 / 2.2e-5          6.7e-6 / 1.8e-5
+#   rotations    7.1e-6 / 2.8e-5          8.0e-6 / 2.1e-5
+#   shs          5.0e-6 / 9.4e-6          4.9e-6 / 8.5e-6
+#   means2D      1.0e-5 / 3.8e-5          1.3e-5 / 7.1e-5
+# Largest 99th percentile over all configurations: 1.56e-5 (largest single row: 2.6e-4, rotations, seed 0, (9, 2))
+# -> bound 1.5e-4.  (Without the robust pixel gradients one flipped 1/255 decision in ONE pixel of one two-camera case
+# lifted the 99th percentile of that case to 4.6e-4.)
+ROW_BOUND = 1.5e-4
+# ... and how many rows may exceed it: 0.5 % of the touched rows of a tensor (2 if that is more), 2 % of the rows of a
+# stratum (1 if that is more).  The reference against itself: at most 1 row of ~710 above the bound.
+ROW_FRAC_ALL, ROW_MIN_ALL = 0.005, 2
+ROW_FRAC_STRATUM, ROW_MIN_STRATUM = 0.02, 1
+
+
+def edge_scene(P=768, W=80, H=48, seed=0, K=16, sh_degree=3, place_cams=None):
+    """small_scene(scale_mu=0.08) with the branches of the per-Gaussian chain rule populated on purpose.  Returns
+    (d, cam, built): d and cam as small_scene does (d gains scale_modifier = 0.8), built = {"A", "B"}: boolean masks
+    of the Gaussians placed below.  WHICH branch a Gaussian takes is decided by the float64 reference: edge_strata().
+
+      A  the first P//4: outside the 1.3 tan(fov/2) limit of the EWA Jacobian -- a third in x only, a third in y only,
+         a third in both (|x/z| resp. |y/z| in [1.35, 1.6] tan(fov/2), random signs, the other axis within 0.9 of the
+         frustum), z in [2, 6], scales 0.25 z exp(0.3 N(0,1)) so that the splat reaches the image, opacity in
+         [0.03, 0.15] so that it does not hide the scene.  place_cams: cameras (same intrinsics) to place them for,
+         in turn; default: the scene's own camera.
+      B  the next P//4: one, two, three or three channels (in turn) of the DC row lowered by [0.3, 0.6] / SH_C0: colour
+         channels clamped at 0.
+      everywhere: higher-order SH of real size (0.3 N(0,1)), non-unit quaternions (length scaled by U[0.5, 2]: the
+      standard mode takes q as given, the RAW mode normalises)."""
+    d, cam = small_scene(P=P, W=W, H=H, seed=seed, K=K, sh_degree=sh_degree, scale_mu=0.08)
+    g = torch.Generator().manual_seed(seed + 4242)
+    U = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64)  # noqa: E731
+    N = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)  # noqa: E731
+    nA = P // 4
+    cams = list(place_cams) if place_cams else [cam]
+    j = torch.arange(nA)
+    which_cam, kind = j % len(cams), (j // len(cams)) % 3          # kind 0: x only, 1: y only, 2: both
+    z = 2.0 + 4.0 * U(nA)
+    out = (1.35 + 0.25 * U(nA, 2)) * torch.where(U(nA, 2) < 0.5, -1.0, 1.0)
+    inside = 0.9 * (2.0 * U(nA, 2) - 1.0)
+    rx = torch.where(kind != 1, out[:, 0], inside[:, 0]) * d["tanfovx"]
+    ry = torch.where(kind != 0, out[:, 1], inside[:, 1]) * d["tanfovy"]
+    pv = torch.stack([rx * z, ry * z, z], 1)
+    means, scales, opac = d["means3D"].clone(), d["scales"].clone(), d["opacities"].clone()
+    for c, cm in enumerate(cams):
+        V = cm.world_view_transform.detach().cpu().double()       # row vectors: view = [x y z 1] @ V
+        world = (pv - V[3, :3]) @ torch.linalg.inv(V[:3, :3])
+        sel = which_cam == c
+        means[:nA][sel] = world[sel].float()
+    scales[:nA] = (0.25 * z[:, None] * torch.exp(0.3 * N(nA, 3))).float()
+    opac[:nA] = (0.03 + 0.12 * U(nA, 1)).float().reshape(opac[:nA].shape)
+    shs = d["shs"].clone()
+    if K > 1:
+        shs[:, 1:] = (0.3 * N(P, K - 1, 3)).float()
+    nch = torch.tensor([1, 2, 3, 3])[torch.arange(nA) % 4]         # how many channels of a B row are lowered
+    rank = torch.argsort(U(nA, 3), dim=1)                          # ... and which: a random permutation per row
+    lower = (0.3 + 0.3 * U(nA, 3)) / SH_C0 * (rank < nch[:, None])
+    shs[nA:2 * nA, 0] -= lower.float()
+    rot = d["rotations"] * (0.5 + 1.5 * U(P, 1)).float()
+    d.update(means3D=means, scales=scales, opacities=opac, shs=shs, rotations=rot, scale_modifier=0.8)
+    built = {"A": torch.arange(P) < nA, "B": (torch.arange(P) >= nA) & (torch.arange(P) < 2 * nA)}
+    return d, cam, built
+
+
+def edge_strata(d, viewmatrix=None, campos=None, sh_degree=None):
+    """The branch every Gaussian takes, by the float64 reference's own rules (oracle/dense_torch.py): boolean numpy
+    masks clamp_x / clamp_y / clamp_xy (view-space x/z, y/z past 1.3 tan(fov/2): in x only, y only, both) and
+    ch1 / ch2 / ch3 (exactly one, two, three colour channels clamped at 0).  Another camera of the same intrinsics:
+    pass its viewmatrix and campos."""
+    from oracle import dense_torch
+    V = (d["viewmatrix"] if viewmatrix is None else viewmatrix).detach().cpu().double().reshape(4, 4)
+    cp = (d["campos"] if campos is None else campos).detach().cpu().double().reshape(3)
+    m = d["means3D"].detach().cpu().double()
+    pv = torch.cat([m, torch.ones(len(m), 1, dtype=torch.float64)], 1) @ V
+    cx = (pv[:, 0] / pv[:, 2]).abs() > 1.3 * d["tanfovx"]
+    cy = (pv[:, 1] / pv[:, 2]).abs() > 1.3 * d["tanfovy"]
+    dirs = m - cp
+    dirs = dirs / dirs.norm(dim=1, keepdim=True)
+    deg = d["sh_degree"] if sh_degree is None else sh_degree
+    col = dense_torch._sh_rgb(deg, d["shs"].detach().cpu().double(), dirs) + 0.5
+    n = (col < 0).sum(1)
+    out = dict(clamp_x=cx & ~cy, clamp_y=cy & ~cx, clamp_xy=cx & cy, ch1=n == 1, ch2=n == 2, ch3=n == 3)
+    out = {k: v.numpy() for k, v in out.items()}
+    out["colour"] = col.numpy()
+    return out
+
+
+STRATA = ("clamp_x", "clamp_y", "clamp_xy", "ch1", "ch2", "ch3")
+
+
+def strata_population(strata, touched, minimum=20, minimum_ch3=3):
+    """{stratum: touched Gaussians in it}; asserts the floor every test relies on (a later change to the builder must
+    not empty a stratum unnoticed)."""
+    pop = {k: int((strata[k] & touched).sum()) for k in STRATA}
+    for k, n in pop.items():
+        assert n >= (minimum_ch3 if k == "ch3" else minimum), f"stratum {k} holds {n} touched Gaussians: {pop}"
+    return pop
+
+
+def row_err(got, ref, touched):
+    """For each touched row i: |got_i - ref_i| / (|ref_i| + s), s = the median row norm of `ref` over the touched rows.
+    A row is touched when the reference's opacity gradient is non-zero.  (Bound and allowance: ROW_BOUND above.)"""
+    ref = np.asarray(ref, dtype=np.float64)
+    ref = ref.reshape(ref.shape[0], -1)[touched]
+    got = np.asarray(got, dtype=np.float64).reshape(-1, ref.shape[1])[touched]
+    n = np.linalg.norm(ref, axis=1)
+    s = float(np.median(n)) if len(n) else 0.0
+    return np.linalg.norm(got - ref, axis=1) / np.maximum(n + s, 1e-300)
+
+
+def row_failures(got, ref, touched, strata=None, bound=None, names=STRATA):
+    """The per-row criterion: -> [(where, rows above the bound, rows, allowed)] for the whole tensor ("all") and each
+    stratum that breaks its allowance; empty = passed."""
+    bound = ROW_BOUND if bound is None else bound
+    err = row_err(got, ref, touched)
+    over = err > bound
+    allowed = max(int(ROW_FRAC_ALL * len(err)), ROW_MIN_ALL)
+    bad = [("all", int(over.sum()), len(err), allowed)] if int(over.sum()) > allowed else []
+    for k in (names if strata is not None else ()):
+        m = strata[k][touched]
+        allowed = max(int(ROW_FRAC_STRATUM * int(m.sum())), ROW_MIN_STRATUM)
+        if int(over[m].sum()) > allowed:
+            bad.append((k, int(over[m].sum()), int(m.sum()), allowed))
+    return bad
+
+
+# Pixels at which the float64 reference comes within this relative distance of another decision (an alpha at 1/255, a
+# running transmittance at 1e-4: render_dense's `margin`) get a zero upstream gradient in the gradient tests, on both
+# sides: a float32 implementation may decide otherwise there, and ONE such pixel moves the rows of every Gaussian it
+# holds (measured: reference float32 against float64, one flipped pixel of 3840 put 16 of 719 opacity rows above
+# ROW_BOUND).  float32 error of an alpha: its exponent reaches ln 255 = 5.5 and carries a few ulps of the conic, whose
+# determinant cancels -> up to ~5e-5 relative; 3e-4 leaves a factor 6 and excludes ~1 % of the pixels (40 of 3840).
+FRAGILE_MARGIN = 3e-4
+
+
+def robust_pixel_grads(out, pixel_grads):
+    """pixel_grads with the pixels zeroed whose decisions are fragile in the reference forward `out` (FRAGILE_MARGIN)."""
+    ok = (out["margin"] >= FRAGILE_MARGIN).to(torch.float64)
+    return tuple(t.double() * ok for t in pixel_grads)
+
+
+def dense_grads(d, rect, pixel_grads, names=("means3D", "opacities", "scales", "rotations", "shs"), dtype=torch.float64,
+                robust=True):
+    """render_dense of the scene dict `d` with `rect` imposed, and autograd gradients of
+    sum(colour gc) + sum(depth gd) + sum(alpha ga) w.r.t. d[names] and the pixel positions; robust: (gc, gd, ga) go
+    through robust_pixel_grads first.
+    -> (outputs, {name: gradient [P, ...], "means2D": [P, 2] in the units of means2D.grad}, the (gc, gd, ga) used)."""
+    from oracle import dense_torch
+    P = d["means3D"].shape[0]
+    leaf = {k: d[k].to(dtype).clone().requires_grad_(True) for k in names}
+    off = torch.zeros(P, 2, dtype=dtype, requires_grad=True)
+    out = dense_torch.render_dense(**{**d, **leaf}, rect=rect, pix_offset=off, dtype=dtype)
+    pixel_grads = robust_pixel_grads(out, pixel_grads) if robust else tuple(t.double() for t in pixel_grads)
+    gc, gd, ga = (t.to(dtype) for t in pixel_grads)
+    ((out["color"] * gc).sum() + (out["depth"] * gd).sum() + (out["alpha"] * ga).sum()).backward()
+    grads = {k: v.grad.reshape(P, -1).double().numpy() for k, v in leaf.items()}
+    grads["means2D"] = (off.grad.double() * torch.tensor([0.5 * d["W"], 0.5 * d["H"]], dtype=torch.float64)).numpy()
+    return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}, grads, pixel_grads
+
+
 def oracle_kwargs(d, **over):
     kw = {k: (v.numpy() if isinstance(v, torch.Tensor) else v) for k, v in d.items()}
     kw.update(over)

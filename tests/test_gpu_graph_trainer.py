@@ -331,3 +331,24 @@ def test_overflow_recovery_grows_repeats_and_matches_a_roomy_run():
     assert rel <= 1e-3, rel
     # no iteration was counted twice: a Gaussian seen in every iteration has been counted n times in both runs
     assert float(tight.model.denom.max()) == float(roomy.model.denom.max()) == n
+
+
+def test_a_dropped_cli_trainer_takes_its_graphs_along_without_the_collector(tmp_path):
+    """train.run's trainer sits in no reference cycle: with the cyclic collector off, its kept graphs are destroyed when the
+    last reference to the result goes.  (torch destroys a captured graph with a device synchronisation, which a capture in
+    progress forbids: a trainer left to the collector could take the process down from inside somebody's later capture.)"""
+    import gc
+    import weakref
+    from binocular3dgs_amd import train
+    src = shutil.copytree(os.path.join(GOLD, "scene_llff"), tmp_path / "scene_llff")
+    gc.collect()
+    gc.disable()
+    try:
+        res = train.run(_train_args(src, tmp_path / "out", ("--step", "graph", "--iterations", "25")))
+        graphs = [weakref.ref(c.graph) for c in res["trainer"]._graphs.values()]
+        trainer = weakref.ref(res["trainer"])
+        assert res["captures"] >= 2 and len(graphs) >= 1 and all(g() is not None for g in graphs)
+        del res
+        assert trainer() is None and all(g() is None for g in graphs)
+    finally:
+        gc.enable()

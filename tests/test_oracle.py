@@ -1,14 +1,17 @@
 """CPU: trust in the oracle itself.  The reference ships no rasterizer source and no tests, so the
 oracle is pinned by (i) analytic known-answer cases KA1-KA8 of SURVEY.md 8c, (ii) an independent
 dense PyTorch restatement (oracle/dense_torch.py) for images AND autograd gradients (KA10),
-(iii) fp64 finite differences through the dense restatement (KA9)."""
+(iii) fp64 finite differences through the dense restatement (KA9), (iv) per-Gaussian gradient parity of the tile oracle at
+the chain rule's rarely reached branches (frustum clamp, SH degree 2/3, clamped colour channels, non-unit quaternions:
+helpers.edge_scene) and a proof by mutation that the per-row criterion used there sees what the per-tensor one misses."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import oracle_kwargs, rel_l2, small_scene
+from helpers import (ROW_BOUND, STRATA, dense_grads, edge_scene, edge_strata, oracle_kwargs, rel_l2, row_failures, small_scene,
+                     row_err, strata_population)
 from oracle import dense_torch, tile_ref
 
 from binocular3dgs_amd.camera import Camera
@@ -186,6 +189,119 @@ def test_ka9_finite_differences_fp64():
             xm[i] -= eps
             num = (loss_of(**{name: xp.reshape(x.shape)}) - loss_of(**{name: xm.reshape(x.shape)})) / (2 * eps)
             assert abs(float(num) - float(ana[i])) <= 1e-4 * max(1.0, abs(float(ana[i]))) + 1e-6, (name, int(i))
+
+
+_TILE_NAMES = {"means3D": "dL_dmeans3D", "opacities": "dL_dopacity", "scales": "dL_dscales", "rotations": "dL_drotations",
+               "shs": "dL_dsh"}
+
+
+def _edge_pixel_grads(W, H, seed):
+    g = torch.Generator().manual_seed(500 + seed)
+    return tuple(torch.randn(c, H, W, generator=g, dtype=torch.float64) for c in (3, 1, 1))
+
+
+@pytest.mark.parametrize("K,deg", [(16, 0), (16, 1), (16, 2), (16, 3), (9, 2)])
+def test_ka11_tile_oracle_vs_dense_autograd_per_gaussian_on_the_edge_scene(K, deg):
+    """tile_ref's hand-derived backward against float64 autograd of the dense restatement, PER GAUSSIAN: frustum-clamped
+    x / y / both, SH degrees 0-3 (also active degree 2 below 16 stored rows), one / two / three colour channels clamped,
+    non-unit quaternions, scale_modifier 0.8.  tile_ref is the yardstick of every GPU parity test.
+    Touched / stratum populations (seed 0, degree 3): helpers.edge_scene, tests/test_gpu_grad_edges.py."""
+    seed = 0
+    d, _, _ = edge_scene(seed=seed, K=K, sh_degree=deg)
+    W, H, P = d["W"], d["H"], d["means3D"].shape[0]
+    st = tile_ref.forward(**oracle_kwargs(d))
+    out, ref, pg = dense_grads(d, torch.from_numpy(st.rect), _edge_pixel_grads(W, H, seed))
+    assert np.array_equal(out["radii"].numpy(), st.radii)
+    for k in ("color", "depth", "alpha"):
+        err = np.abs(out[k].numpy() - getattr(st, k)) / (1 + np.abs(getattr(st, k)))
+        assert err.max() < 3e-5, k
+    touched = ref["opacities"][:, 0] != 0
+    strata = edge_strata(d)
+    pop = strata_population(strata, touched)
+    gr = tile_ref.backward(st, *(t.numpy() for t in pg))
+    got = {k: gr[n].reshape(P, -1) for k, n in _TILE_NAMES.items()}
+    got["means2D"] = gr["dL_dmeans2D"][:, :2]
+    print(f"K={K} degree={deg}: touched {int(touched.sum())} {pop}")
+    for k, r in ref.items():
+        assert rel_l2(got[k], r) <= 2e-4, k
+        for s in STRATA:
+            m = strata[s] & touched
+            if np.abs(r[m]).max() > 0:
+                assert rel_l2(got[k][m], r[m]) <= 2e-4, (k, s)
+        assert row_failures(got[k], r, touched, strata) == [], k
+    assert float(np.abs(gr["dL_dsh"][:, (deg + 1) ** 2:]).max(initial=0.0)) == 0.0
+
+
+def _mutations():
+    """name -> (attribute of oracle.dense_torch, replacement factory(original), strata in which the per-row criterion
+    must fail, tensor looked at)"""
+    def unfrozen_clamp(orig):
+        return lambda t: t
+
+    def frozen_direction_above_degree_1(orig):
+        def sh(deg, sh_, d):
+            lo = min(deg, 1)
+            return orig(lo, sh_, d) + (orig(deg, sh_, d.detach()) - orig(lo, sh_, d.detach()))
+        return sh
+
+    def straight_through_colour_clamp(orig):
+        return lambda v: v + (orig(v) - v).detach()
+
+    def normalised_quaternion(orig):
+        return lambda scales, mod, q: orig(scales, mod, torch.nn.functional.normalize(q))
+
+    return {"clamped tx/ty not a constant": ("_const", unfrozen_clamp, ("clamp_x", "clamp_y", "clamp_xy"), "means3D"),
+            "view direction frozen in the degree >= 2 terms": ("_sh_rgb", frozen_direction_above_degree_1, ("all",), "means3D"),
+            "colour clamp passed straight through": ("_clamp_rgb", straight_through_colour_clamp, ("ch1", "ch2", "ch3"), "shs"),
+            "quaternion normalised before the covariance": ("_cov3d", normalised_quaternion, ("all",), "rotations")}
+
+
+def test_ka12_per_row_criterion_catches_mutations_the_per_tensor_criterion_misses(monkeypatch):
+    """Four wrong chain rules, made by monkeypatching the dense restatement, against the right one on edge_scene
+    (seed 0, K = 16, degree 3).  Each must break the per-row criterion (helpers.row_failures, the bound and allowance the
+    kernels are held to) in its strata, and so must the same fault put into only 20 touched Gaussians of those strata.
+    What the per-tensor criterion (relative L2 <= 2e-4, the only one until now) says is printed; as measured:
+                                                        whole scene               in 20 Gaussians only
+      clamped tx/ty not a constant                      caught (means3D 8.5e-3)   MISSED (1.4e-5; per row: 17 rows over)
+      view direction frozen in the degree >= 2 terms    caught (means3D 6.4e-2)   MISSED (2.8e-6; per row: 11 rows over)
+      colour clamp passed straight through              caught (shs 5.7e-1)       caught (2.7e-2; per row: 19 rows over)
+      quaternion normalised before the covariance       caught (every tensor)     caught (8.0e-2; per row: 20 rows over)
+    On edge_scene the per-tensor criterion sees all four as whole-scene faults -- the scene was built so that these terms
+    are large; on the scenes of the older tests it could not (no clamped Gaussian is touched there, SH degree <= 1, the
+    whole view-direction term is 2x-6x the tolerance) -- and it misses the first two once they are confined to a few
+    Gaussians, which is what a kernel that is wrong in one rare branch looks like."""
+    seed = 0
+    d, _, _ = edge_scene(seed=seed)
+    st = tile_ref.forward(**oracle_kwargs(d))
+    rect = torch.from_numpy(st.rect)
+    _, ref, pg = dense_grads(d, rect, _edge_pixel_grads(d["W"], d["H"], seed))
+    touched = ref["opacities"][:, 0] != 0
+    strata = edge_strata(d)
+    strata_population(strata, touched)
+    _, g32, _ = dense_grads(d, rect, pg, dtype=torch.float32, robust=False)
+    for k, r in ref.items():      # the criterion passes the right chain rule evaluated in float32
+        assert row_failures(g32[k], r, touched, strata) == [], k
+    for name, (attr, make, where, tensor) in _mutations().items():
+        with monkeypatch.context() as mp:
+            mp.setattr(dense_torch, attr, make(getattr(dense_torch, attr)))
+            _, mut, _ = dense_grads(d, rect, pg, robust=False)
+        failed = {f[0]: f for f in row_failures(mut[tensor], ref[tensor], touched, strata)}
+        old = {k: rel_l2(mut[k], ref[k]) for k in ref}
+        caught_old = sorted(k for k, e in old.items() if e > 2e-4)
+        print(f"{name}: per-row fails in {sorted(failed)} ({tensor}); per-tensor 2e-4 "
+              f"{'catches ' + ', '.join(f'{k} {old[k]:.1e}' for k in caught_old) if caught_old else 'MISSES it'}")
+        for s in where:
+            assert s in failed, (name, s, failed)
+        # the same fault in only 20 touched Gaussians of those strata (the ones with the smallest reference rows): what a
+        # kernel that is wrong in one rare branch looks like
+        pool = touched if where == ("all",) else (np.any([strata[s] for s in where], axis=0) & touched)
+        idx = np.nonzero(pool)[0]
+        idx = idx[np.argsort(np.linalg.norm(ref[tensor][idx], axis=1))[:20]]
+        few = ref[tensor].copy()
+        few[idx] = mut[tensor][idx]
+        e, n_over = rel_l2(few, ref[tensor]), int((row_err(few, ref[tensor], touched) > ROW_BOUND).sum())
+        print(f"    in 20 rows only: per-tensor {e:.1e} ({'caught' if e > 2e-4 else 'MISSED'}), per-row: {n_over} rows over")
+        assert row_failures(few, ref[tensor], touched, strata) != [], (name, "20 rows")
 
 
 def test_empty_inputs():
