@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("B3GS_LIB") or os.path.join(_HERE, "libb3gs_raster.so")   # B3GS_LIB: A/B builds of the kernels
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 OK = 0
 ERR_NAMES = {-1: "B3GS_ERR_ARG", -2: "B3GS_ERR_ALLOC", -3: "B3GS_ERR_HIP", -4: "B3GS_ERR_CAPACITY",
              -5: "B3GS_ERR_NO_DEVICE"}
@@ -167,7 +167,12 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # ABI 16: baseline JPEG of rendered frames
            "b3gs_jpeg_workspace_bytes", "b3gs_jpeg_encode_batch",
            # ABI 17: TSDF fusion and marching tetrahedra
-           "b3gs_tsdf_integrate_batch", "b3gs_mesh_workspace_bytes", "b3gs_mesh_count", "b3gs_mesh_emit")
+           "b3gs_tsdf_integrate_batch", "b3gs_mesh_workspace_bytes", "b3gs_mesh_count", "b3gs_mesh_emit",
+           # ABI 18: cleaning and scoring an extracted mesh
+           "b3gs_mesh_components", "b3gs_mesh_clean_workspace_bytes", "b3gs_mesh_clean_count", "b3gs_mesh_clean_emit",
+           "b3gs_mesh_sample_workspace_bytes", "b3gs_mesh_sample_count", "b3gs_mesh_sample_emit",
+           "b3gs_nearest_workspace_bytes", "b3gs_nearest_grid", "b3gs_nearest_query",
+           "b3gs_cloud_score_workspace_bytes", "b3gs_cloud_score")
 
 _lib = None
 
@@ -307,6 +312,30 @@ def lib():
     L.b3gs_mesh_count.restype = C.c_int
     L.b3gs_mesh_emit.argtypes = [C.POINTER(B3gsTsdfVolume), V, I64, I64, V, V, V, V]
     L.b3gs_mesh_emit.restype = C.c_int
+    L.b3gs_mesh_components.argtypes = [I32, I64, V, V, V, V]
+    L.b3gs_mesh_components.restype = C.c_int
+    L.b3gs_mesh_clean_workspace_bytes.argtypes = [I64, I64]
+    L.b3gs_mesh_clean_workspace_bytes.restype = C.c_size_t
+    L.b3gs_mesh_clean_count.argtypes = [I32, I64, V, V, V, V, V, V]
+    L.b3gs_mesh_clean_count.restype = C.c_int
+    L.b3gs_mesh_clean_emit.argtypes = [I32, I64, V, V, V, V, V, V, V, I64, I64, V, V, V, V]
+    L.b3gs_mesh_clean_emit.restype = C.c_int
+    L.b3gs_mesh_sample_workspace_bytes.argtypes = [I64]
+    L.b3gs_mesh_sample_workspace_bytes.restype = C.c_size_t
+    L.b3gs_mesh_sample_count.argtypes = [I32, I64, V, V, F, V, V]
+    L.b3gs_mesh_sample_count.restype = C.c_int
+    L.b3gs_mesh_sample_emit.argtypes = [I32, I64, V, V, F, V, I64, V, V]
+    L.b3gs_mesh_sample_emit.restype = C.c_int
+    L.b3gs_nearest_workspace_bytes.argtypes = [I64]
+    L.b3gs_nearest_workspace_bytes.restype = C.c_size_t
+    L.b3gs_nearest_grid.argtypes = [I64, V, F, V, V]
+    L.b3gs_nearest_grid.restype = C.c_int
+    L.b3gs_nearest_query.argtypes = [I64, V, I64, F, V, V, V]
+    L.b3gs_nearest_query.restype = C.c_int
+    L.b3gs_cloud_score_workspace_bytes.argtypes = [I64]
+    L.b3gs_cloud_score_workspace_bytes.restype = C.c_size_t
+    L.b3gs_cloud_score.argtypes = [I64, V, V, F, V, V, V]
+    L.b3gs_cloud_score.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

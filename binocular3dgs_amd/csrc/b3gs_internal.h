@@ -216,6 +216,81 @@ __device__ __forceinline__ uint32_t open_tiles(uint2 rc, const OpenMap& om) {
     for (uint32_t wb = x0 >> 6; wb <= (x1 - 1u) >> 6; wb++) n += (uint32_t)__builtin_popcountll(open_bits(om, y, wb, x0, x1, &c0));
   return n;
 }
+
+// ---- ordered compaction (mesh.hip, meshtools.hip): ranks inside a workgroup, then an exclusive scan of the block sums -------
+// The number of counts (each < 2^BITS) of the block's threads in front of this one, in thread order, and the block's sum.
+// Every thread of the block (TPB_ threads) calls it; wave_n holds TPB_ / 64 words of LDS.
+template <int TPB_, int BITS>
+__device__ __forceinline__ int b3gs_block_rank(int cnt, int* wave_n, int* total) {
+  const int lane = threadIdx.x & (B3GS_WAVE - 1), wv = threadIdx.x / B3GS_WAVE;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int before = 0, all = 0;
+#pragma unroll
+  for (int bit = 0; bit < BITS; bit++) {
+    const unsigned long long m = __ballot((cnt >> bit) & 1);
+    before += __popcll(m & below) << bit;
+    all += __popcll(m) << bit;
+  }
+  if (lane == 0) wave_n[wv] = all;
+  __syncthreads();
+  int sum = 0;
+#pragma unroll
+  for (int w = 0; w < TPB_ / B3GS_WAVE; w++) {
+    if (w < wv) before += wave_n[w];
+    sum += wave_n[w];
+  }
+  *total = sum;
+  return before;
+}
+// inclusive scan of one word per lane across the wave
+__device__ __forceinline__ uint32_t b3gs_wave_scan(uint32_t val, int lane) {
+  for (int d = 1; d < B3GS_WAVE; d <<= 1) {
+    const uint32_t o = __shfl_up(val, d);
+    if (lane >= d) val += o;
+  }
+  return val;
+}
+// The same for counts of any size (32-bit sums, which wrap): -> the sum of the threads in front, *total = the block's sum.
+template <int TPB_>
+__device__ __forceinline__ uint32_t b3gs_block_exscan(uint32_t val, uint32_t* wave_n, uint32_t* total) {
+  const int lane = threadIdx.x & (B3GS_WAVE - 1), wv = threadIdx.x / B3GS_WAVE;
+  const uint32_t incl = b3gs_wave_scan(val, lane);
+  if (lane == B3GS_WAVE - 1) wave_n[wv] = incl;
+  __syncthreads();
+  uint32_t before = incl - val, sum = 0u;
+#pragma unroll
+  for (int w = 0; w < TPB_ / B3GS_WAVE; w++) {
+    if (w < wv) before += wave_n[w];
+    sum += wave_n[w];
+  }
+  *total = sum;
+  return before;
+}
+// Exclusive scan of nb block sums in place by ONE workgroup of B3GS_SCAN_TPB threads, 1024 sums per step; the sum of all of
+// them -> *total as int64.  The scanned offsets are 32-bit words: they wrap only when the total does not fit 32 bits.
+#define B3GS_SCAN_TPB 1024
+__device__ __forceinline__ void b3gs_scan_block_sums(uint32_t* sums, int nb, int64_t* total) {
+  __shared__ uint32_t wave_n[B3GS_SCAN_TPB / B3GS_WAVE];
+  __shared__ unsigned long long carry;
+  if (threadIdx.x == 0) carry = 0ull;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int b0 = 0; b0 < nb; b0 += B3GS_SCAN_TPB) {
+    const int b = b0 + threadIdx.x;
+    const uint32_t val = b < nb ? sums[b] : 0u;
+    const uint32_t incl = b3gs_wave_scan(val, lane);
+    if (lane == 63) wave_n[wv] = incl;
+    __syncthreads();
+    const unsigned long long start = carry;
+    uint32_t before = 0u;
+    for (int w = 0; w < wv; w++) before += wave_n[w];
+    if (b < nb) sums[b] = (uint32_t)start + before + incl - val;
+    __syncthreads();
+    if (threadIdx.x == B3GS_SCAN_TPB - 1) carry = start + before + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *total = (int64_t)carry;
+}
 #endif
 
 // ---- error reporting shared by every translation unit (api.hip owns the thread-local message) -------

@@ -20,7 +20,7 @@
 namespace {
 
 constexpr int TPB = 256;
-constexpr int SCAN_TPB = 1024;
+constexpr int SCAN_TPB = B3GS_SCAN_TPB;
 constexpr int NV = B3GS_MAX_TSDF_VIEWS;
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -168,29 +168,8 @@ struct MeshArgs {
   int32_t* faces;
 };
 
-// The number of counts (each < 16) of the block's threads in front of this one, in thread order, and the block's sum.
-// Every thread of the block calls it.
-__device__ __forceinline__ int block_rank(int cnt, int* wave_n, int* total) {
-  const int lane = threadIdx.x & (B3GS_WAVE - 1), wv = threadIdx.x / B3GS_WAVE;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int before = 0, all = 0;
-#pragma unroll
-  for (int bit = 0; bit < 4; bit++) {
-    const unsigned long long m = __ballot((cnt >> bit) & 1);
-    before += __popcll(m & below) << bit;
-    all += __popcll(m) << bit;
-  }
-  if (lane == 0) wave_n[wv] = all;
-  __syncthreads();
-  int sum = 0;
-#pragma unroll
-  for (int w = 0; w < TPB / B3GS_WAVE; w++) {
-    if (w < wv) before += wave_n[w];
-    sum += wave_n[w];
-  }
-  *total = sum;
-  return before;
-}
+// (the ranks inside a block and the scan of the block sums: b3gs_internal.h, shared with meshtools.hip)
+__device__ __forceinline__ int block_rank(int cnt, int* wave_n, int* total) { return b3gs_block_rank<TPB, 4>(cnt, wave_n, total); }
 
 __device__ __forceinline__ size_t corner_offset(const B3gsTsdfVolume& g, int c) {
   return (size_t)(c & 1) + (size_t)(c >> 1 & 1) * g.nx + (size_t)(c >> 2) * g.nx * g.ny;
@@ -263,31 +242,7 @@ __global__ void __launch_bounds__(TPB) edges_kernel(MeshArgs a) {
 // block 0: vertices, block 1: triangles.  The scanned offsets are 32-bit words: they wrap only when the total does not fit
 // int32, which the caller refuses before anything is emitted.
 __global__ void __launch_bounds__(SCAN_TPB) scan_kernel(MeshArgs a) {
-  __shared__ uint32_t wave_n[SCAN_TPB / B3GS_WAVE];
-  __shared__ unsigned long long carry;
-  uint32_t* sums = a.bsum + (size_t)blockIdx.x * a.nb;
-  if (threadIdx.x == 0) carry = 0ull;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int b0 = 0; b0 < a.nb; b0 += SCAN_TPB) {
-    const int b = b0 + threadIdx.x;
-    const uint32_t val = b < a.nb ? sums[b] : 0u;
-    uint32_t incl = val;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(incl, d);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_n[wv] = incl;
-    __syncthreads();
-    const unsigned long long start = carry;
-    uint32_t before = 0u;
-    for (int w = 0; w < wv; w++) before += wave_n[w];
-    if (b < a.nb) sums[b] = (uint32_t)start + before + incl - val;
-    __syncthreads();
-    if (threadIdx.x == SCAN_TPB - 1) carry = start + before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.totals[blockIdx.x] = (int64_t)carry;
+  b3gs_scan_block_sums(a.bsum + (size_t)blockIdx.x * a.nb, a.nb, a.totals + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(TPB) vertices_kernel(MeshArgs a) {

@@ -1,0 +1,63 @@
+"""python -m binocular3dgs_amd.eval_mesh --mesh MESH.ply --gt CLOUD.ply --spacing S --max_dist D --tau T
+                                         [--keep_largest K] [--min_triangles M]
+
+Scores a triangle mesh (the files mesh.write_mesh_ply writes) against a reference point cloud (any PLY whose vertex element
+has x, y, z), on the device: the mesh is optionally cleaned (mesh_tools.clean), sampled at `spacing` (the vertices plus a
+lattice per triangle) and compared with the cloud both ways by nearest point-to-point distance capped at `max_dist`:
+accuracy, completeness, chamfer, and precision, recall and F-score at `tau`.  Prints the dict and writes mesh_results.json
+next to the mesh.
+
+This is the measure of the DTU surface benchmark WITHOUT its protocol: the 0.2 mm thinning of both clouds, the observation
+mask and the ground plane belong to the caller, who owns those files (mesh_tools.score_clouds takes the masks).  The numbers
+printed here are not DTU numbers.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="score a triangle mesh against a reference point cloud (point-to-point, both ways)")
+    p.add_argument("--mesh", required=True)
+    p.add_argument("--gt", required=True)
+    p.add_argument("--spacing", type=float, required=True, help="lattice spacing of the points sampled on the mesh")
+    p.add_argument("--max_dist", type=float, required=True, help="distances are capped here")
+    p.add_argument("--tau", type=float, required=True, help="threshold of precision / recall / F-score")
+    p.add_argument("--keep_largest", type=int, default=0)
+    p.add_argument("--min_triangles", type=int, default=0)
+    return p
+
+
+def run(mesh_path: str, gt_path: str, spacing: float, max_dist: float, tau: float, keep_largest: int = 0, min_triangles: int = 0,
+        device="cuda") -> dict:
+    from . import mesh, mesh_tools
+    from .init_points import read_ply_vertices
+    v, c, f = mesh.read_mesh_ply(mesh_path)
+    rows = read_ply_vertices(gt_path)
+    gt = torch.from_numpy(np.stack([rows["x"], rows["y"], rows["z"]], axis=1).astype(np.float32)).to(device)
+    vertices, colours, faces = torch.from_numpy(v).to(device), torch.from_numpy(c).to(device), torch.from_numpy(f).to(device)
+    if keep_largest or min_triangles:
+        vertices, colours, faces = mesh_tools.clean(vertices, colours, faces, keep_largest, min_triangles)
+    result = mesh_tools.score_mesh(vertices, faces, gt, spacing, max_dist, tau)
+    result.update({"mesh": os.path.abspath(mesh_path), "gt": os.path.abspath(gt_path), "spacing": spacing,
+                   "vertices": int(vertices.shape[0]), "triangles": int(faces.shape[0]), "keep_largest": keep_largest,
+                   "min_triangles": min_triangles})
+    with open(os.path.join(os.path.dirname(os.path.abspath(mesh_path)), "mesh_results.json"), "w") as fp:
+        json.dump(result, fp, indent=2)
+    return result
+
+
+def main(argv=None) -> int:
+    a = parser().parse_args(argv)
+    print(json.dumps(run(a.mesh, a.gt, a.spacing, a.max_dist, a.tau, a.keep_largest, a.min_triangles)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,11 +1,13 @@
 """python -m binocular3dgs_amd.extract_mesh -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--views train|test|all]
                                             [--resolution 256 | --voxel_size S] [--truncation_voxels 4] [--alpha_min 0.5]
                                             [--min_weight 1] [--bounds x0 y0 z0 x1 y1 z1]
+                                            [--keep_largest 0] [--min_triangles 0]
 
 A triangle mesh of a trained model: the point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply is rendered from
 the chosen cameras, depth, alpha and colour are fused into a TSDF volume and the zero level set is extracted, all on the
 device (mesh.fuse_model).  Writes <model_path>/mesh/iteration_<it>/mesh.ply (binary PLY, coloured vertices) and prints the
-voxel, vertex and triangle counts.
+voxel, vertex and triangle counts.  --keep_largest K keeps the K components with the most triangles (ties at the K-th
+all survive), --min_triangles M the components with at least M (mesh_tools.clean); with both at 0 the step is not run.
 
 The model and the cameras are found the way spiral.py finds them: source path, images folder, image resolution, background,
 SH degree, dataset name and view count come from <model_path>/cfg_args; the command line wins.  A model folder whose dataset
@@ -37,6 +39,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--alpha_min", type=float, default=0.5)
     p.add_argument("--min_weight", type=float, default=1.0)
     p.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    p.add_argument("--keep_largest", type=int, default=0, help="keep the K largest connected components (0: all)")
+    p.add_argument("--min_triangles", type=int, default=0, help="drop the components with fewer triangles (0: none)")
     return p
 
 
@@ -73,7 +77,8 @@ def load_cameras(model_path: str, cfg: dict, source_path, views: str, device="cu
 
 
 def run(model_path: str, source_path=None, iteration: int = -1, views: str = "train", resolution=None, voxel_size=None,
-        truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, bounds=None) -> str:
+        truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, bounds=None,
+        keep_largest: int = 0, min_triangles: int = 0) -> str:
     from . import mesh
     from .gaussian_model import GaussianModel
     from .spiral import max_iteration, read_cfg_args
@@ -90,6 +95,11 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
     vertices, colours, faces, vol = mesh.fuse_model(
         model, cams, bg, resolution=resolution, voxel_size=voxel_size, bounds=None if bounds is None else (bounds[:3], bounds[3:]),
         truncation_voxels=truncation_voxels, alpha_min=alpha_min, min_weight=min_weight, return_volume=True)
+    if keep_largest or min_triangles:
+        from . import mesh_tools
+        vertices, colours, faces, st = mesh_tools.clean(vertices, colours, faces, keep_largest, min_triangles, return_stats=True)
+        print(f"{st['components']} components, {st['kept']} kept: dropped {st['vertices_dropped']} vertices, "
+              f"{st['triangles_dropped']} triangles")
     out_dir = os.path.join(model_path, "mesh", "iteration_{}".format(it))
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "mesh.ply")
@@ -104,7 +114,7 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
 def main(argv=None) -> int:
     a = parser().parse_args(argv)
     run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
-        a.min_weight, a.bounds)
+        a.min_weight, a.bounds, a.keep_largest, a.min_triangles)
     return 0
 
 

@@ -1,0 +1,158 @@
+"""Cleaning and scoring an extracted mesh, on the device (csrc/meshtools.hip, ABI 18).
+
+    labels, tri_count = components(vertices, faces)                      # int32 [V] each; no host read
+    vertices, colours, faces = clean(vertices, colours, faces, keep_largest=1)
+    points = sample_surface(vertices, faces, spacing)                    # the vertices, then a lattice per triangle
+    d = nearest_distances(a, b, max_dist)                                # float32 [Na]: the float32 brute force, bit for bit
+    score = score_clouds(recon, gt, max_dist, tau)                       # accuracy, completeness, chamfer, precision, recall, fscore
+    score = score_mesh(vertices, faces, gt, spacing, max_dist, tau)
+
+The arithmetic is stated in include/b3gs_raster.h and restated in numpy by tests/meshtools_ref.py.  Policy that is not hot
+lives here in torch: the component threshold of `clean` (a topk of the triangle counts, kept on the device).
+
+The score is the point-to-point measure of the DTU surface benchmark (distances both ways between points on the
+reconstruction and a reference cloud).  DTU's own protocol -- thinning both clouds to 0.2 mm, the observation mask, the
+ground plane -- stays with the caller, who owns those files: `mask_recon` / `mask_gt` are the hook.  Numbers computed here
+without that protocol are not DTU numbers.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+MAX_LATTICE = 1 << 15      # n1, n2 of sample_surface stay below this
+
+
+def _faces(faces) -> torch.Tensor:
+    if faces.dtype != torch.int32:
+        raise ValueError("faces are int32 [F, 3]")
+    return faces
+
+
+def components(vertices_or_V, faces: torch.Tensor):
+    """-> (labels int32 [V], tri_count int32 [V]) on the device.  labels[v] is the smallest vertex index of v's component
+    (two vertices are connected when one triangle names both); tri_count[r] is the number of triangles of the component whose
+    label is r and 0 elsewhere.  The first argument is the vertex tensor or V itself.  No host read (capturable)."""
+    from . import _C
+    V = int(vertices_or_V) if isinstance(vertices_or_V, int) else int(vertices_or_V.shape[0])
+    return _C.mesh_components(V, _faces(faces))
+
+
+def component_threshold(tri_count: torch.Tensor, keep_largest: int = 0, min_triangles: int = 0) -> torch.Tensor:
+    """One int32 on the device: max(min_triangles, 1, c_k), c_k the triangle count of the keep_largest-th largest component
+    (ties at c_k all survive; keep_largest = 0: no such bound).  No host read."""
+    if keep_largest < 0 or min_triangles < 0:
+        raise ValueError("keep_largest and min_triangles are not negative")
+    thr = torch.full((1,), max(int(min_triangles), 1), dtype=torch.int32, device=tri_count.device)
+    if keep_largest > 0 and tri_count.numel() > 0:
+        k = min(int(keep_largest), tri_count.numel())
+        thr = torch.maximum(thr, torch.topk(tri_count, k).values[k - 1:k])
+    return thr
+
+
+def clean(vertices: torch.Tensor, colours: torch.Tensor, faces: torch.Tensor, keep_largest: int = 0, min_triangles: int = 0,
+          return_stats: bool = False):
+    """Keeps the components with at least max(min_triangles, 1, c_k) triangles and drops the vertices no kept triangle names
+    -> (vertices, colours, faces), order and winding preserved.  One host read: the totals, between count and emit."""
+    from . import _C
+    labels, tri_count = components(vertices, faces)
+    thr = component_threshold(tri_count, keep_largest, min_triangles)
+    ws, totals = _C.mesh_clean_count(faces, labels, tri_count, thr)
+    if return_stats:                                   # (one read still: the statistics ride along with the totals)
+        ncomp = ((tri_count > 0).sum()).reshape(1)
+        kept = ((tri_count >= thr) & (tri_count > 0)).sum().reshape(1)
+        nverts, ntris, bad, ncomp, kept = torch.cat([totals, ncomp, kept]).tolist()
+    else:
+        nverts, ntris, bad = totals.tolist()
+    if bad:
+        raise ValueError(f"clean: {bad} triangles name a vertex outside 0 .. {vertices.shape[0] - 1}")
+    out = _C.mesh_clean_emit(vertices, colours, faces, labels, tri_count, thr, ws, nverts, ntris)
+    if return_stats:
+        return out + ({"components": ncomp, "kept": kept, "vertices_dropped": vertices.shape[0] - nverts,
+                       "triangles_dropped": faces.shape[0] - ntris},)
+    return out
+
+
+def sample_surface(vertices: torch.Tensor, faces: torch.Tensor, spacing: float) -> torch.Tensor:
+    """float32 [N, 3]: the V vertices in order, then per triangle (p0, p1, p2) the lattice p0 + i/(n1+1) e1 + j/(n2+1) e2,
+    n = floor(|e| / spacing), inside the triangle and off its far edge, in (triangle, i, j) order.  Errors, not clamps:
+    spacing <= 0, an n at or above 2^15, more than 2^31 - 1 points.  One host read: the total (and the error counts)."""
+    from . import _C
+    if not spacing > 0.0:
+        raise ValueError("sample_surface: the spacing is positive")
+    ws, totals = _C.mesh_sample_count(vertices, _faces(faces), float(spacing))
+    npoints, over, bad = totals.tolist()
+    if bad:
+        raise ValueError(f"sample_surface: {bad} triangles name a vertex outside 0 .. {vertices.shape[0] - 1}")
+    if over:
+        raise ValueError(f"sample_surface: {over} triangles have an edge of {MAX_LATTICE} spacings or more (or not finite): use a larger spacing")
+    if vertices.shape[0] + npoints > 2 ** 31 - 1:
+        raise ValueError(f"sample_surface: {vertices.shape[0] + npoints} points do not fit int32: use a larger spacing")
+    return _C.mesh_sample_emit(vertices, faces, float(spacing), ws, npoints)
+
+
+class NearestGrid:
+    """The search grid over a cloud `b` (float32 [Nb, 3], Nb >= 1) for distances up to max_dist; query(a) -> float32 [Na].
+    Built and queried without a host read.  params() reads the grid the device chose (a diagnostic: one host read)."""
+
+    def __init__(self, b: torch.Tensor, max_dist: float):
+        from . import _C
+        if b.shape[0] < 1:
+            raise ValueError("nearest_distances: the cloud searched is empty")
+        self.nb, self.max_dist = int(b.shape[0]), float(max_dist)
+        self._ws = _C.nearest_grid(b, self.max_dist)
+
+    def query(self, a: torch.Tensor) -> torch.Tensor:
+        from . import _C
+        return _C.nearest_query(a, self._ws, self.nb, self.max_dist)
+
+    def params(self) -> dict:
+        head = self._ws[:32].cpu()
+        f, i = head.view(torch.float32), head.view(torch.int32)
+        return {"origin": f[:3].tolist(), "cell": float(f[3]), "dims": i[4:7].tolist(), "shells": int(i[7])}
+
+
+def nearest_distances(a: torch.Tensor, b: torch.Tensor, max_dist: float) -> torch.Tensor:
+    """out[i] = min(max_dist, sqrt(min_j |a_i - b_j|^2)) in float32, equal to the brute force bit for bit.  An empty `b` is an
+    error.  No host read."""
+    return NearestGrid(b, max_dist).query(a)
+
+
+def _mask(mask, n, device):
+    if mask is None:
+        return None
+    if mask.dtype != torch.bool or mask.shape != (n,):
+        raise ValueError("a mask is a bool tensor with one value per point")
+    return mask.to(device)
+
+
+def score_clouds(recon: torch.Tensor, gt: torch.Tensor, max_dist: float, tau: float, mask_recon: Optional[torch.Tensor] = None,
+                 mask_gt: Optional[torch.Tensor] = None, return_distances: bool = False) -> dict:
+    """accuracy = mean distance recon -> gt, completeness = mean distance gt -> recon (each capped at max_dist), chamfer their
+    mean; precision / recall = the share of recon / gt distances below tau, fscore their harmonic mean (0 when both are 0).
+    A mask drops points from the means, never from the cloud being searched.  One host read: six fp64 words."""
+    from . import _C
+    if recon.shape[0] < 1 or gt.shape[0] < 1:
+        raise ValueError("score_clouds: both clouds hold at least one point")
+    d_recon = nearest_distances(recon, gt, max_dist)
+    d_gt = nearest_distances(gt, recon, max_dist)
+    sums = torch.empty((2, 3), dtype=torch.float64, device=recon.device)
+    _C.cloud_score(d_recon, _mask(mask_recon, recon.shape[0], recon.device), float(tau), sums[0])
+    _C.cloud_score(d_gt, _mask(mask_gt, gt.shape[0], gt.device), float(tau), sums[1])
+    (sa, na, ta), (sc, nc, tc) = sums.tolist()                    # the one host read
+    if na == 0 or nc == 0:
+        raise ValueError("score_clouds: a mask leaves no point")
+    p, r = ta / na, tc / nc
+    out = {"accuracy": sa / na, "completeness": sc / nc, "chamfer": 0.5 * (sa / na + sc / nc), "precision": p, "recall": r,
+           "fscore": 2.0 * p * r / (p + r) if p + r > 0.0 else 0.0, "n_recon": int(na), "n_gt": int(nc),
+           "n_recon_below_tau": int(ta), "n_gt_below_tau": int(tc), "max_dist": float(max_dist), "tau": float(tau)}
+    if return_distances:
+        out["d_recon"], out["d_gt"] = d_recon, d_gt
+    return out
+
+
+def score_mesh(vertices: torch.Tensor, faces: torch.Tensor, gt: torch.Tensor, spacing: float, max_dist: float, tau: float,
+               mask_gt: Optional[torch.Tensor] = None, return_distances: bool = False) -> dict:
+    """sample_surface(vertices, faces, spacing), then score_clouds against gt."""
+    return score_clouds(sample_surface(vertices, faces, spacing), gt, max_dist, tau, None, mask_gt, return_distances)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define B3GS_ABI_VERSION 17
+#define B3GS_ABI_VERSION 18
 #define B3GS_TILE 16 /* 16x16-pixel tiles: the binning granularity (bit-exact with the oracle) */
 
 typedef enum B3gsStatus {
@@ -724,6 +724,67 @@ size_t b3gs_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int b3gs_mesh_count(const B3gsTsdfVolume* volume, float min_weight, void* workspace, b3gs_stream_t stream);
 int b3gs_mesh_emit(const B3gsTsdfVolume* volume, void* workspace, int64_t nverts, int64_t ntris, float* vertices,
                    uint8_t* colours, int32_t* faces, b3gs_stream_t stream);
+
+/* ---- cleaning and scoring an extracted mesh (ABI 18; binocular3dgs_amd/mesh_tools.py) -----------
+ * Integer work, minima over sets and single correctly rounded float32 operations: tests/meshtools_ref.py restates every
+ * statement in numpy, and everything below except the fp64 means agrees bit for bit.  Nothing synchronises or reads the
+ * device; every call is capturable in a graph.  Every workspace is 256-byte aligned; a size function returns 0 for bad sizes.
+ *
+ * b3gs_mesh_components: faces int32 [F, 3] over vertices 0 .. V-1.  Two vertices are connected when one triangle names
+ * both (a repeated index is legal).  labels[v] = the smallest vertex index of v's component; tri_count[r] = the triangles of
+ * the component whose label is r, 0 at every index that is not a label; a vertex no triangle names is its own component
+ * with 0 triangles.  A triangle with an index outside 0 .. V-1 connects nothing and is counted nowhere.  Lock-free
+ * union-find, one thread per triangle edge; four launches, no thread waits for another.
+ *
+ * b3gs_mesh_clean_count / _emit: a component survives when tri_count >= max(*threshold, 1) (threshold: ONE int32 on the
+ * device).  A vertex is kept when its component survives (so it has a triangle), a triangle when its component survives.
+ * New vertex ids are the exclusive scan of the kept flags; kept vertices, colours and triangles keep their order and winding.
+ * count leaves three int64 at the START of the workspace: {vertices kept, triangles kept, triangles with an index outside
+ * 0 .. V-1}; emit(nverts, ntris) fills out_vertices [nverts, 3], out_colours [nverts, 3], out_faces [ntris, 3] and writes
+ * nothing past those counts.  emit takes the arguments of count again and the same workspace.
+ *
+ * b3gs_mesh_sample_count / _emit: points = the V vertices in order, then per triangle (p0, p1, p2), in triangle order:
+ *   e1 = p1 - p0, e2 = p2 - p0                                              per component
+ *   |e| = sqrt((e.x e.x + e.y e.y) + e.z e.z)
+ *   n1 = floor(|e1| / spacing), n2 = floor(|e2| / spacing)                  both < 2^15, else the triangle is counted as an error
+ *   for i = 0 .. n1, for j = 0 .. n2, without (0, 0), where i (n2+1) + j (n1+1) < (n1+1)(n2+1)   (integers)
+ *     point = (p0 + (i / (n1+1)) e1) + (j / (n2+1)) e2                      i / (n1+1) and j / (n2+1) are float32 divisions
+ * count leaves three int64 at the start of the workspace: {lattice points (without the V vertices), triangles past the 2^15
+ * limit, triangles with an index outside 0 .. V-1}; emit(npoints) writes points [V + npoints, 3].  spacing > 0;
+ * V + npoints <= 2^31 - 1.
+ *
+ * b3gs_nearest_grid / _query: out[i] = min(max_dist, sqrt(min_j d2(a_i, b_j))), d = a - b per component,
+ * d2 = (d.x d.x + d.y d.y) + d.z d.z, all float32: the float32 brute force, bit for bit.  grid sorts b (Nb >= 1 points)
+ * into a uniform grid whose origin, edge and dimensions are computed on the device and left at the start of the workspace as
+ * {float origin[3], float edge, int32 dim[3], int32 shells}; the edge is the largest of cbrt(box volume / (8 Nb)) (square
+ * root / quotient when the box is flat along one / two axes), max_dist / 16 and extent / 1000, widened until the grid has at
+ * most 1024 cells per axis and min(max(8 Nb, 4096), 2^24) cells.  query walks shells of cells outward from the query's cell
+ * and stops at the first shell that provably holds nothing nearer than the best so far or max_dist (csrc/meshtools.hip states
+ * the bound); at most `shells` <= 17 shells.  max_dist > 0 and finite; the coordinates are finite.
+ *
+ * b3gs_cloud_score: out[0] = the fp64 sum of dist[i] over the points with mask[i] != 0 (mask NULL: all), out[1] = their
+ * number, out[2] = the number of them with dist[i] < tau.  Per-workgroup fp64 partials, folded in index order by one wave:
+ * the same bits on every call. */
+int b3gs_mesh_components(int32_t V, int64_t F, const int32_t* faces, int32_t* labels, int32_t* tri_count, b3gs_stream_t stream);
+size_t b3gs_mesh_clean_workspace_bytes(int64_t V, int64_t F);
+int b3gs_mesh_clean_count(int32_t V, int64_t F, const int32_t* faces, const int32_t* labels, const int32_t* tri_count,
+                          const int32_t* threshold, void* workspace, b3gs_stream_t stream);
+int b3gs_mesh_clean_emit(int32_t V, int64_t F, const float* vertices, const uint8_t* colours, const int32_t* faces,
+                         const int32_t* labels, const int32_t* tri_count, const int32_t* threshold, void* workspace,
+                         int64_t nverts, int64_t ntris, float* out_vertices, uint8_t* out_colours, int32_t* out_faces,
+                         b3gs_stream_t stream);
+size_t b3gs_mesh_sample_workspace_bytes(int64_t F);
+int b3gs_mesh_sample_count(int32_t V, int64_t F, const float* vertices, const int32_t* faces, float spacing, void* workspace,
+                           b3gs_stream_t stream);
+int b3gs_mesh_sample_emit(int32_t V, int64_t F, const float* vertices, const int32_t* faces, float spacing, void* workspace,
+                          int64_t npoints, float* points, b3gs_stream_t stream);
+size_t b3gs_nearest_workspace_bytes(int64_t Nb);
+int b3gs_nearest_grid(int64_t Nb, const float* b, float max_dist, void* workspace, b3gs_stream_t stream);
+int b3gs_nearest_query(int64_t Na, const float* a, int64_t Nb, float max_dist, const void* workspace, float* out,
+                       b3gs_stream_t stream);
+size_t b3gs_cloud_score_workspace_bytes(int64_t N);
+int b3gs_cloud_score(int64_t N, const float* dist, const uint8_t* mask, float tau, double* out, void* workspace,
+                     b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
