@@ -217,9 +217,40 @@ __device__ __forceinline__ uint32_t open_tiles(uint2 rc, const OpenMap& om) {
   return n;
 }
 
-// ---- ordered compaction (mesh.hip, meshtools.hip): ranks inside a workgroup, then an exclusive scan of the block sums -------
-// The number of counts (each < 2^BITS) of the block's threads in front of this one, in thread order, and the block's sum.
-// Every thread of the block (TPB_ threads) calls it; wave_n holds TPB_ / 64 words of LDS.
+// ---- wave and workgroup primitives of the feature modules (cloud, sweep, jpeg, metrics, frames, mesh, meshtools, knn) -------
+// One wave is 64 lanes; every lane of the wave (every thread of the workgroup, for the b3gs_block_* ones) makes the call.
+// xor butterfly 32, 16, .., 1: every lane gets the result, in one fixed tree (int, uint32_t, unsigned long long, float, double)
+template <typename T>
+__device__ __forceinline__ T b3gs_wave_sum(T v) {
+#pragma unroll
+  for (int d = B3GS_WAVE / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, B3GS_WAVE);
+  return v;
+}
+__device__ __forceinline__ float b3gs_wave_min(float v) {
+#pragma unroll
+  for (int d = B3GS_WAVE / 2; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, B3GS_WAVE));
+  return v;
+}
+__device__ __forceinline__ float b3gs_wave_max(float v) {
+#pragma unroll
+  for (int d = B3GS_WAVE / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, B3GS_WAVE));
+  return v;
+}
+// inclusive scan of one value per lane across the wave (int, uint32_t, unsigned long long; sums wrap)
+template <typename T>
+__device__ __forceinline__ T b3gs_wave_scan(T val, int lane) {
+#pragma unroll
+  for (int d = 1; d < B3GS_WAVE; d <<= 1) {
+    const T o = __shfl_up(val, d, B3GS_WAVE);
+    if (lane >= d) val += o;
+  }
+  return val;
+}
+
+// Ordered compaction: ranks inside a workgroup, then an exclusive scan of the block sums.
+// b3gs_block_rank: the number of counts (each < 2^BITS) of the block's threads in front of this one, in thread order, and the
+// block's sum.  BITS == 1 is a keep flag: one ballot.  wave_n holds TPB_ / 64 words of LDS, written WITHOUT a barrier in
+// front: a caller that ranks again in a loop puts a __syncthreads() between two calls (grow_append_kernel of cloud.hip).
 template <int TPB_, int BITS>
 __device__ __forceinline__ int b3gs_block_rank(int cnt, int* wave_n, int* total) {
   const int lane = threadIdx.x & (B3GS_WAVE - 1), wv = threadIdx.x / B3GS_WAVE;
@@ -242,22 +273,17 @@ __device__ __forceinline__ int b3gs_block_rank(int cnt, int* wave_n, int* total)
   *total = sum;
   return before;
 }
-// inclusive scan of one word per lane across the wave
-__device__ __forceinline__ uint32_t b3gs_wave_scan(uint32_t val, int lane) {
-  for (int d = 1; d < B3GS_WAVE; d <<= 1) {
-    const uint32_t o = __shfl_up(val, d);
-    if (lane >= d) val += o;
-  }
-  return val;
-}
-// The same for counts of any size (32-bit sums, which wrap): -> the sum of the threads in front, *total = the block's sum.
-template <int TPB_>
-__device__ __forceinline__ uint32_t b3gs_block_exscan(uint32_t val, uint32_t* wave_n, uint32_t* total) {
+// The same for counts of any size (uint32_t or unsigned long long sums, which wrap): -> the sum of the threads in front,
+// *total = the block's sum.  Safe to call in a loop: the barrier in front of the LDS write keeps a second call from replacing
+// wave_n while a slow wave still reads the sums of the first.
+template <int TPB_, typename T>
+__device__ __forceinline__ T b3gs_block_exscan(T val, T* wave_n, T* total) {
   const int lane = threadIdx.x & (B3GS_WAVE - 1), wv = threadIdx.x / B3GS_WAVE;
-  const uint32_t incl = b3gs_wave_scan(val, lane);
+  const T incl = b3gs_wave_scan(val, lane);
+  __syncthreads();
   if (lane == B3GS_WAVE - 1) wave_n[wv] = incl;
   __syncthreads();
-  uint32_t before = incl - val, sum = 0u;
+  T before = incl - val, sum = 0;
 #pragma unroll
   for (int w = 0; w < TPB_ / B3GS_WAVE; w++) {
     if (w < wv) before += wave_n[w];
@@ -266,30 +292,69 @@ __device__ __forceinline__ uint32_t b3gs_block_exscan(uint32_t val, uint32_t* wa
   *total = sum;
   return before;
 }
-// Exclusive scan of nb block sums in place by ONE workgroup of B3GS_SCAN_TPB threads, 1024 sums per step; the sum of all of
-// them -> *total as int64.  The scanned offsets are 32-bit words: they wrap only when the total does not fit 32 bits.
+// Exclusive scan of nb block sums (32-bit words, signed or not) in place by ONE workgroup of B3GS_SCAN_TPB threads, 1024 sums
+// per step; the sum of all of them, exact in 64 bits, -> *total narrowed to its type.  The scanned offsets are 32-bit words:
+// they wrap only when the total does not fit 32 bits.
 #define B3GS_SCAN_TPB 1024
-__device__ __forceinline__ void b3gs_scan_block_sums(uint32_t* sums, int nb, int64_t* total) {
-  __shared__ uint32_t wave_n[B3GS_SCAN_TPB / B3GS_WAVE];
-  __shared__ unsigned long long carry;
-  if (threadIdx.x == 0) carry = 0ull;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+template <typename W, typename T>
+__device__ __forceinline__ void b3gs_scan_block_sums(W* sums, int nb, T* total) {
+  static_assert(sizeof(W) == sizeof(uint32_t), "32-bit block sums");
+  __shared__ unsigned long long wave_n[B3GS_SCAN_TPB / B3GS_WAVE];
+  unsigned long long carry = 0ull;
   for (int b0 = 0; b0 < nb; b0 += B3GS_SCAN_TPB) {
     const int b = b0 + threadIdx.x;
-    const uint32_t val = b < nb ? sums[b] : 0u;
-    const uint32_t incl = b3gs_wave_scan(val, lane);
-    if (lane == 63) wave_n[wv] = incl;
-    __syncthreads();
-    const unsigned long long start = carry;
-    uint32_t before = 0u;
-    for (int w = 0; w < wv; w++) before += wave_n[w];
-    if (b < nb) sums[b] = (uint32_t)start + before + incl - val;
-    __syncthreads();
-    if (threadIdx.x == B3GS_SCAN_TPB - 1) carry = start + before + incl;
-    __syncthreads();
+    unsigned long long chunk;
+    const unsigned long long before = b3gs_block_exscan<B3GS_SCAN_TPB>((unsigned long long)(b < nb ? (uint32_t)sums[b] : 0u), wave_n, &chunk);
+    if (b < nb) sums[b] = (W)(uint32_t)(carry + before);
+    carry += chunk;
   }
-  if (threadIdx.x == 0) *total = (int64_t)carry;
+  if (threadIdx.x == 0) *total = (T)carry;
+}
+
+// The bounding box of a workgroup's points: per-thread bounds lo[3], hi[3] (changed) -> threads k = 0..5 get bound k (0..2 the
+// minima, 3..5 the maxima) of the whole workgroup, every other thread an unspecified value.  red: TPB_ / 64 rows of LDS.
+template <int TPB_>
+__device__ __forceinline__ float b3gs_block_bbox(float (&lo)[3], float (&hi)[3], float (*red)[6]) {
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    lo[a] = b3gs_wave_min(lo[a]);
+    hi[a] = b3gs_wave_max(hi[a]);
+  }
+  if ((threadIdx.x & (B3GS_WAVE - 1)) == 0)
+    for (int a = 0; a < 3; a++) {
+      red[threadIdx.x / B3GS_WAVE][a] = lo[a];
+      red[threadIdx.x / B3GS_WAVE][3 + a] = hi[a];
+    }
+  __syncthreads();
+  float v = 0.0f;
+  if (threadIdx.x < 6) {
+    v = red[0][threadIdx.x];
+    for (int w = 1; w < TPB_ / B3GS_WAVE; w++) v = threadIdx.x < 3 ? fminf(v, red[w][threadIdx.x]) : fmaxf(v, red[w][threadIdx.x]);
+  }
+  return v;
+}
+
+// Deterministic float64 sums in two passes.  Pass 1, a workgroup of 256 threads: NQ_ per-thread doubles -> one row of NQ_
+// (written by threads 0 .. NQ_ - 1) in the fixed tree butterfly, then (wave 0 + wave 1) + (wave 2 + wave 3).  red: 4 rows of LDS.
+template <int TPB_, int NQ_>
+__device__ __forceinline__ void b3gs_block_sum_f64(const double (&q)[NQ_], double (*red)[NQ_], double* row) {
+  static_assert(TPB_ == 4 * B3GS_WAVE, "the tree is written for four waves");
+#pragma unroll
+  for (int k = 0; k < NQ_; k++) {
+    const double s = b3gs_wave_sum(q[k]);
+    if ((threadIdx.x & (B3GS_WAVE - 1)) == 0) red[threadIdx.x / B3GS_WAVE][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NQ_) {
+    const int k = threadIdx.x;
+    row[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+  }
+}
+// Pass 2, ONE wave: the sum of part[b * stride], b < n -- lane l adds b = l, l + 64, .. in order, then the butterfly.
+__device__ __forceinline__ double b3gs_wave_fold_f64(const double* part, int n, int stride) {
+  double s = 0.0;
+  for (int b = threadIdx.x; b < n; b += B3GS_WAVE) s += part[(size_t)b * stride];
+  return b3gs_wave_sum(s);
 }
 #endif
 

@@ -189,14 +189,9 @@ struct TriArgs {
 
 __device__ __forceinline__ void block_count_store(bool keep, int32_t* block_count) {
   __shared__ int wave_n[TPB / B3GS_WAVE];
-  const unsigned long long b = __ballot(keep);
-  if ((threadIdx.x & (B3GS_WAVE - 1)) == 0) wave_n[threadIdx.x / B3GS_WAVE] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < TPB / B3GS_WAVE; w++) s += wave_n[w];
-    block_count[blockIdx.x] = s;
-  }
+  int total;
+  b3gs_block_rank<TPB, 1>(keep, wave_n, &total);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(TPB) triangulate_kernel(TriArgs a) {
@@ -278,30 +273,8 @@ __global__ void __launch_bounds__(TPB) sheet_kernel(SheetArgs a) {
 }
 
 // one block: exclusive scan of the block counts in place, the total to *count
-__global__ void __launch_bounds__(1024) scan_blocks_kernel(int32_t* block_count, int nb, int32_t* count) {
-  __shared__ int wave_n[16];
-  __shared__ int carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int b0 = 0; b0 < nb; b0 += 1024) {
-    const int b = b0 + threadIdx.x;
-    const int v = b < nb ? block_count[b] : 0;
-    int incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_n[wv] = incl;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wv; w++) before += wave_n[w];
-    if (b < nb) block_count[b] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count = carry;
+__global__ void __launch_bounds__(B3GS_SCAN_TPB) scan_blocks_kernel(int32_t* block_count, int nb, int32_t* count) {
+  b3gs_scan_block_sums(block_count, nb, count);
 }
 
 __global__ void __launch_bounds__(TPB) compact_kernel(const Rec* rec, int n, const int32_t* block_offset, float* points, uint8_t* colors) {
@@ -310,13 +283,9 @@ __global__ void __launch_bounds__(TPB) compact_kernel(const Rec* rec, int n, con
   Rec r = {0.f, 0.f, 0.f, 0u};
   if (i < n) r = rec[i];
   const bool keep = (r.rgbk >> 24) != 0u;
-  const unsigned long long b = __ballot(keep);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) wave_n[wv] = __popcll(b);
-  __syncthreads();
+  int total;
+  const int slot = block_offset[blockIdx.x] + b3gs_block_rank<TPB, 1>(keep, wave_n, &total);
   if (!keep) return;
-  int slot = block_offset[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wv; w++) slot += wave_n[w];
   if (slot >= n) return;                                                          // (cannot happen: the outputs hold n rows)
   points[3 * (size_t)slot] = r.x;
   points[3 * (size_t)slot + 1] = r.y;
@@ -354,12 +323,6 @@ __global__ void __launch_bounds__(TPB) grow_count_kernel(B3gsCloudGrow g) {
                g.cy, u, w);
   const int cell = grid_cell(u, w, g.W, g.H);
   if (cell >= 0) atomicAdd(g.grids + (size_t)v * (g.H + 2) * (g.W + 2) + cell, 1);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 // one wave per candidate; block = 4 waves
@@ -410,9 +373,9 @@ __global__ void __launch_bounds__(TPB) grow_ssim_kernel(GrowArgs a) {
   double mean = 0.0;
 #pragma unroll
   for (int ch = 0; ch < 3; ch++) {
-    const double mu1 = wave_sum(acc[ch][0]), mu2 = wave_sum(acc[ch][1]);
-    const double s1 = wave_sum(acc[ch][2]) - mu1 * mu1, s2 = wave_sum(acc[ch][3]) - mu2 * mu2;
-    const double s12 = wave_sum(acc[ch][4]) - mu1 * mu2;
+    const double mu1 = b3gs_wave_sum(acc[ch][0]), mu2 = b3gs_wave_sum(acc[ch][1]);
+    const double s1 = b3gs_wave_sum(acc[ch][2]) - mu1 * mu1, s2 = b3gs_wave_sum(acc[ch][3]) - mu2 * mu2;
+    const double s12 = b3gs_wave_sum(acc[ch][4]) - mu1 * mu2;
     const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
     mean += ((2.0 * mu1 * mu2 + C1) * (2.0 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2));
   }
@@ -439,7 +402,6 @@ __global__ void __launch_bounds__(TPB) grow_ssim_kernel(GrowArgs a) {
 __global__ void __launch_bounds__(APPEND_TPB) grow_append_kernel(GrowArgs a) {
   const B3gsCloudGrow& g = a.io;
   __shared__ int wave_n[APPEND_TPB / B3GS_WAVE];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int ncand = g.n_seeds * g.n_samples;
   const size_t gs = (size_t)(g.H + 2) * (g.W + 2);
   for (int c = threadIdx.x; c < ncand; c += APPEND_TPB) {
@@ -461,14 +423,8 @@ __global__ void __launch_bounds__(APPEND_TPB) grow_append_kernel(GrowArgs a) {
     const int c = c0 + threadIdx.x;
     const int state = c < ncand ? a.sel[c] : 0;
     const bool acc = state == 2;
-    const unsigned long long b = __ballot(acc);
-    if (lane == 0) wave_n[wv] = __popcll(b);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int w = 0; w < APPEND_TPB / B3GS_WAVE; w++) {
-      if (w < wv) before += wave_n[w];
-      total += wave_n[w];
-    }
+    int total;
+    const int before = b3gs_block_rank<APPEND_TPB, 1>(acc, wave_n, &total);
     if (state == 1) {
       const int cr = grid_cell(a.uv[4 * (size_t)c], a.uv[4 * (size_t)c + 1], g.W, g.H);
       const int cs = grid_cell(a.uv[4 * (size_t)c + 2], a.uv[4 * (size_t)c + 3], g.W, g.H);
@@ -476,7 +432,7 @@ __global__ void __launch_bounds__(APPEND_TPB) grow_append_kernel(GrowArgs a) {
       if (cs >= 0) atomicSub(g.grids + g.src * gs + cs, 1);
     }
     if (acc) {
-      const long long slot = (long long)base + before + __popcll(b & ((1ull << lane) - 1ull));
+      const long long slot = (long long)base + before;
       float px, py, pz;
       candidate_of(g, c, px, py, pz);
       if (slot < g.capacity) {
@@ -513,7 +469,7 @@ extern "C" size_t b3gs_cloud_workspace_bytes(int64_t n) {
 
 static int launch_compaction(Rec* rec, int32_t* block_count, int n, float* points, uint8_t* colors, int32_t* count, hipStream_t s) {
   const int nb = (int)nblocks(n);
-  hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, s, block_count, nb, count);
+  hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(B3GS_SCAN_TPB), 0, s, block_count, nb, count);
   if (nb > 0) hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(TPB), 0, s, (const Rec*)rec, n, (const int32_t*)block_count, points, colors);
   return 0;
 }

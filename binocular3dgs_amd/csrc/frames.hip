@@ -100,22 +100,11 @@ __device__ __forceinline__ uint32_t quant(float x) {
   return (uint32_t)t;
 }
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-
 // min / max of a block's values -> every thread
 __device__ float2 block_minmax(float mn, float mx) {
   __shared__ float2 red[TPB / 64];
-  mn = wave_min(mn);
-  mx = wave_max(mx);
+  mn = b3gs_wave_min(mn);
+  mx = b3gs_wave_max(mx);
   const int wave = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[wave] = make_float2(mn, mx);

@@ -11,26 +11,15 @@ namespace b3 {
 
 static const char* kDeviceOnly = "the matcher cloud is built on the HIP device only";
 
-static Tensor dev_of(const Tensor& t, at::ScalarType type, const char* name, const at::Device* dev = nullptr) {
-  if (!t.defined() || !t.is_cuda()) raise(std::string(name) + " is on " + (t.defined() ? t.device().str() : "no device") + ": " + kDeviceOnly);
-  if (dev && t.device() != *dev) raise(std::string(name) + " is on " + t.device().str() + ", not on " + dev->str());
-  if (t.scalar_type() != type) throw py::value_error(std::string(name) + ": wrong dtype");
-  return t.is_contiguous() ? t : t.contiguous();
-}
-
 static Tensor matrix(const Tensor& t, int64_t r, int64_t c, const char* name, const at::Device& dev) {
-  Tensor m = dev_of(t, at::kFloat, name, &dev);
+  Tensor m = dev_input(t, at::kFloat, name, kDeviceOnly, &dev).contiguous();
   if (m.dim() != 2 || m.size(0) != r || m.size(1) != c)
     throw py::value_error(std::string(name) + " is a float32 [" + std::to_string(r) + ", " + std::to_string(c) + "] matrix");
   return m;
 }
 
-static Tensor workspace(int64_t n, const at::Device& dev) {
-  return at::empty({(int64_t)b3gs_cloud_workspace_bytes(n)}, at::TensorOptions().dtype(at::kByte).device(dev));
-}
-
 static Tensor image_hwc3(const Tensor& t, const char* name, const at::Device* dev = nullptr) {
-  Tensor im = dev_of(t, at::kByte, name, dev);
+  Tensor im = dev_input(t, at::kByte, name, kDeviceOnly, dev).contiguous();
   if (im.dim() != 3 || im.size(2) != 3 || im.size(0) < 2 || im.size(1) < 2)
     throw py::value_error(std::string(name) + " is a uint8 [H, W, 3] image of at least 2 x 2 pixels");
   return im;
@@ -45,19 +34,20 @@ static std::tuple<Tensor, Tensor, Tensor> triangulate_matches(const Tensor& proj
   Tensor pr = matrix(proj_ref, 3, 4, "proj_ref", dev), ps = matrix(proj_src, 3, 4, "proj_src", dev);
   Tensor k = matrix(intrinsic, 3, 3, "intrinsic", dev);
   Tensor wr = matrix(w2c_ref, 4, 4, "w2c_ref", dev), wsrc = matrix(w2c_src, 4, 4, "w2c_src", dev);
-  Tensor a = dev_of(kp_ref, at::kFloat, "kp_ref", &dev), b = dev_of(kp_src, at::kFloat, "kp_src", &dev);
+  Tensor a = dev_input(kp_ref, at::kFloat, "kp_ref", kDeviceOnly, &dev).contiguous();
+  Tensor b = dev_input(kp_src, at::kFloat, "kp_src", kDeviceOnly, &dev).contiguous();
   if (a.dim() != 2 || a.size(1) != 2 || b.dim() != 2 || b.size(1) != 2 || a.size(0) != b.size(0))
     throw py::value_error("triangulate_matches: kp_ref and kp_src are float32 [N, 2] with the same N");
   const int64_t N = a.size(0);
   Tensor points = at::empty({N, 3}, a.options());
   Tensor colors = at::empty({N, 3}, im.options());
   Tensor count = at::empty({1}, a.options().dtype(at::kInt));
-  Tensor ws = workspace(N, dev);
+  Tensor ws = byte_workspace(b3gs_cloud_workspace_bytes(N), dev);
   {
     DeviceGuard g(dev);
     check(b3gs_triangulate_matches((int32_t)N, fptr(pr), fptr(ps), fptr(k), fptr(wr), fptr(wsrc), fptr(a), fptr(b),
                                    im.data_ptr<uint8_t>(), (int32_t)im.size(1), (int32_t)im.size(0), (float)reproj_threshold,
-                                   N ? points.data_ptr<float>() : nullptr, N ? colors.data_ptr<uint8_t>() : nullptr,
+                                   ptr_or_null<float>(points), ptr_or_null<uint8_t>(colors),
                                    count.data_ptr<int32_t>(), ws.data_ptr(), cur_stream(dev)),
           "b3gs_triangulate_matches");
   }
@@ -73,7 +63,7 @@ static std::tuple<Tensor, Tensor, Tensor> background_sheet(const Tensor& image, 
   Tensor points = at::empty({n, 3}, ik.options());
   Tensor colors = at::empty({n, 3}, im.options());
   Tensor count = at::empty({1}, ik.options().dtype(at::kInt));
-  Tensor ws = workspace(n, dev);
+  Tensor ws = byte_workspace(b3gs_cloud_workspace_bytes(n), dev);
   {
     DeviceGuard g(dev);
     check(b3gs_background_sheet(im.data_ptr<uint8_t>(), (int32_t)im.size(1), (int32_t)im.size(0), fptr(ik), fptr(e), (float)depth,
@@ -90,12 +80,13 @@ static void cloud_grow_round(const Tensor& images, const Tensor& w2c, const Tens
                              int64_t n_start, int64_t h_patch_size, bool init, double fx, double fy, double cx, double cy,
                              double alpha, double ssim_threshold, const c10::optional<Tensor>& debug_ssim,
                              const c10::optional<Tensor>& debug_mask) {
-  Tensor im = dev_of(images, at::kByte, "cloud_grow_round: images");
+  Tensor im = dev_input(images, at::kByte, "cloud_grow_round: images", kDeviceOnly).contiguous();
   const at::Device dev = im.device();
   if (im.dim() != 4 || im.size(3) != 3) throw py::value_error("cloud_grow_round: images is uint8 [n_views, H, W, 3]");
   const int64_t V = im.size(0), H = im.size(1), W = im.size(2);
-  Tensor m = dev_of(w2c, at::kFloat, "w2c", &dev), win = dev_of(window, at::kFloat, "window", &dev);
-  Tensor si = dev_of(seed_idx, at::kInt, "seed_idx", &dev), nz = dev_of(noise, at::kFloat, "noise", &dev);
+  Tensor m = dev_input(w2c, at::kFloat, "w2c", kDeviceOnly, &dev).contiguous(), win = dev_input(window, at::kFloat, "window", kDeviceOnly, &dev).contiguous();
+  Tensor si = dev_input(seed_idx, at::kInt, "seed_idx", kDeviceOnly, &dev).contiguous();
+  Tensor nz = dev_input(noise, at::kFloat, "noise", kDeviceOnly, &dev).contiguous();
   if (m.dim() != 3 || m.size(0) != V || m.size(1) != 4 || m.size(2) != 4) throw py::value_error("cloud_grow_round: w2c is float32 [n_views, 4, 4]");
   if (h_patch_size != 5) raise("cloud_grow_round: h_patch_size=5 (an 11x11 window) is the only supported patch");
   if (win.numel() != 121) throw py::value_error("cloud_grow_round: window holds 121 weights");
@@ -123,7 +114,7 @@ static void cloud_grow_round(const Tensor& images, const Tensor& w2c, const Tens
     if (!dbg_m.is_cuda() || dbg_m.scalar_type() != at::kByte || !dbg_m.is_contiguous() || dbg_m.numel() != ncand)
       throw py::value_error("cloud_grow_round: debug_mask is a contiguous uint8 [candidates] tensor on the device");
   }
-  Tensor ws = workspace(ncand, dev);
+  Tensor ws = byte_workspace(b3gs_cloud_workspace_bytes(ncand), dev);
   B3gsCloudGrow io = {};
   io.W = (int32_t)W;
   io.H = (int32_t)H;

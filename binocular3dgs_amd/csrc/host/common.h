@@ -45,6 +45,24 @@ inline at::Tensor dev_f32(const at::Tensor& t, const char* name, const char* wha
   at::Tensor r = t.scalar_type() == at::kFloat ? t : t.to(at::kFloat);
   return r.is_contiguous() ? r : r.contiguous();
 }
+// A defined tensor of dtype `type` on the HIP device (and on `*dev`), as passed: NOT made contiguous -- a caller that reads
+// it through a raw pointer says .contiguous(), one that writes it in place checks is_contiguous().  Device errors are
+// B3gsError ("<name> is on cpu: <device_only_msg>"), a wrong dtype is a ValueError.
+inline at::Tensor dev_input(const at::Tensor& t, at::ScalarType type, const char* name, const char* device_only_msg,
+                            const at::Device* dev = nullptr) {
+  if (!t.defined() || !t.is_cuda()) raise(std::string(name) + " is on " + (t.defined() ? t.device().str() : "no device") + ": " + device_only_msg);
+  if (dev && t.device() != *dev) raise(std::string(name) + " is on " + t.device().str() + ", not on " + dev->str());
+  if (t.scalar_type() != type) throw pybind11::value_error(std::string(name) + ": wrong dtype");
+  return t;
+}
+// an uninitialised workspace of `bytes` bytes on `dev`
+inline at::Tensor byte_workspace(size_t bytes, const at::Device& dev) {
+  return at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+}
+// the first n 64-bit words of a byte workspace as an int64 [n] view (the device-side totals of a count call)
+inline at::Tensor head_words(const at::Tensor& ws, int n) { return ws.slice(0, 0, 8 * n).view(at::kLong); }
+template <typename T>
+inline T* ptr_or_null(const at::Tensor& t) { return t.numel() ? t.data_ptr<T>() : nullptr; }
 inline const float* fptr(const at::Tensor& t) { return (t.defined() && t.numel()) ? t.data_ptr<float>() : nullptr; }
 inline float* fptr_mut(at::Tensor& t) { return (t.defined() && t.numel()) ? t.data_ptr<float>() : nullptr; }
 

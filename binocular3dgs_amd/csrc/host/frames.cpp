@@ -75,7 +75,7 @@ static void encode_frames(const std::vector<Tensor>& renders, const py::object& 
     v.cmap_out = out_ptr(cmap_out, i, H, W);
   }
   const size_t ws_bytes = b3gs_frames_workspace_bytes((int32_t)n, (int32_t)H, (int32_t)W);
-  Tensor ws = at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+  Tensor ws = byte_workspace(ws_bytes, dev);
   {
     DeviceGuard g(dev);
     check(b3gs_encode_frames_batch((int32_t)n, tab.data(), (int32_t)H, (int32_t)W, percentile, lut.data_ptr<uint8_t>(),

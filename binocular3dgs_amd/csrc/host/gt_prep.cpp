@@ -70,7 +70,7 @@ static std::vector<std::tuple<Tensor, c10::optional<Tensor>, c10::optional<Tenso
     out.emplace_back(image, alpha, bg);
   }
   const size_t ws_bytes = b3gs_gt_workspace_bytes((int32_t)n, tab.data(), (int32_t)H, (int32_t)W);
-  Tensor ws = at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+  Tensor ws = byte_workspace(ws_bytes, dev);
   {
     DeviceGuard g(dev);
     check(b3gs_prepare_gt_batch((int32_t)n, tab.data(), (int32_t)H, (int32_t)W, white_background ? 1 : 0, (float)dtu_threshold,

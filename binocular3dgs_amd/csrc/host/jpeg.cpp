@@ -38,7 +38,7 @@ static void jpeg_encode(const std::vector<Tensor>& images, const Tensor& qtables
   if (!lengths.is_cuda() || lengths.scalar_type() != at::kLong || !lengths.is_contiguous() || lengths.numel() < n)
     throw py::value_error("jpeg_encode: lengths must be a contiguous int64 tensor of n elements on the device");
   const size_t ws_bytes = b3gs_jpeg_workspace_bytes((int32_t)n, (int32_t)H, (int32_t)W);
-  Tensor ws = at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+  Tensor ws = byte_workspace(ws_bytes, dev);
   {
     DeviceGuard g(dev);
     check(b3gs_jpeg_encode_batch((int32_t)n, ptrs.data(), (int32_t)H, (int32_t)W,

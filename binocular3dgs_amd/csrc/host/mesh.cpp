@@ -13,19 +13,12 @@ namespace b3 {
 
 static const char* kMeshDeviceOnly = "the mesh extraction runs on the HIP device only";
 
-static Tensor mesh_input(const Tensor& t, at::ScalarType type, const char* name, const at::Device* dev = nullptr) {
-  if (!t.defined() || !t.is_cuda()) raise(std::string(name) + " is on " + (t.defined() ? t.device().str() : "no device") + ": " + kMeshDeviceOnly);
-  if (dev && t.device() != *dev) raise(std::string(name) + " is on " + t.device().str() + ", not on " + dev->str());
-  if (t.scalar_type() != type) throw py::value_error(std::string(name) + ": wrong dtype");
-  return t;
-}
-
 // the volume tensors are written in place: they must be contiguous as they are
 static B3gsTsdfVolume volume_of(Tensor& tsdf, Tensor& weight, Tensor& rgb, const std::vector<double>& origin, double voxel, const char* what) {
-  mesh_input(tsdf, at::kFloat, "tsdf");
+  dev_input(tsdf, at::kFloat, "tsdf", kMeshDeviceOnly);
   const at::Device dev = tsdf.device();
-  mesh_input(weight, at::kFloat, "weight", &dev);
-  mesh_input(rgb, at::kFloat, "rgb", &dev);
+  dev_input(weight, at::kFloat, "weight", kMeshDeviceOnly, &dev);
+  dev_input(rgb, at::kFloat, "rgb", kMeshDeviceOnly, &dev);
   if (tsdf.dim() != 3 || weight.sizes() != tsdf.sizes() || rgb.dim() != 4 || rgb.size(3) != 3 || rgb.sizes().slice(0, 3) != tsdf.sizes())
     throw py::value_error(std::string(what) + ": tsdf and weight are float32 [nz, ny, nx], rgb is float32 [nz, ny, nx, 3]");
   if (!tsdf.is_contiguous() || !weight.is_contiguous() || !rgb.is_contiguous())
@@ -61,8 +54,8 @@ static void tsdf_integrate(Tensor tsdf, Tensor weight, Tensor rgb, std::vector<d
   B3gsTsdfView views[B3GS_MAX_TSDF_VIEWS] = {};
   int64_t H = 0, W = 0;
   for (size_t v = 0; v < n; v++) {
-    Tensor d = mesh_input(depths[v], at::kFloat, "depth", &dev), a = mesh_input(alphas[v], at::kFloat, "alpha", &dev);
-    Tensor c = mesh_input(colours[v], at::kFloat, "colour", &dev);
+    Tensor d = dev_input(depths[v], at::kFloat, "depth", kMeshDeviceOnly, &dev), a = dev_input(alphas[v], at::kFloat, "alpha", kMeshDeviceOnly, &dev);
+    Tensor c = dev_input(colours[v], at::kFloat, "colour", kMeshDeviceOnly, &dev);
     if (c.dim() != 3 || c.size(0) != 3) throw py::value_error("tsdf_integrate: a colour image is float32 [3, H, W]");
     if (v == 0) H = c.size(1), W = c.size(2);
     if (c.size(1) != H || c.size(2) != W || d.numel() != H * W || a.numel() != H * W || H < 1 || W < 1 || H > INT32_MAX || W > INT32_MAX)
@@ -82,24 +75,20 @@ static void tsdf_integrate(Tensor tsdf, Tensor weight, Tensor rgb, std::vector<d
                                   cur_stream(dev)), "b3gs_tsdf_integrate_batch");
 }
 
-static Tensor mesh_workspace(const Tensor& tsdf) {
-  const size_t bytes = b3gs_mesh_workspace_bytes((int32_t)tsdf.size(2), (int32_t)tsdf.size(1), (int32_t)tsdf.size(0));
-  return at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(tsdf.device()));
-}
-
 // -> (workspace, totals): totals is the int64 [2] view {vertices, triangles} of the head of the workspace, on the device
 static std::tuple<Tensor, Tensor> mesh_count(Tensor tsdf, Tensor weight, Tensor rgb, std::vector<double> origin, double voxel, double min_weight,
                                              c10::optional<Tensor> workspace) {
   static const char* what = "mesh_count";
   B3gsTsdfVolume g = volume_of(tsdf, weight, rgb, origin, voxel, what);
   const at::Device dev = tsdf.device();
-  Tensor ws = workspace.has_value() ? mesh_input(*workspace, at::kByte, "workspace", &dev) : mesh_workspace(tsdf);
+  Tensor ws = workspace.has_value() ? dev_input(*workspace, at::kByte, "workspace", kMeshDeviceOnly, &dev)
+                                    : byte_workspace(b3gs_mesh_workspace_bytes(g.nx, g.ny, g.nz), dev);
   if ((size_t)ws.numel() < b3gs_mesh_workspace_bytes(g.nx, g.ny, g.nz) || !ws.is_contiguous()) throw py::value_error("mesh_count: the workspace is too small");
   {
     DeviceGuard guard(dev);
     check(b3gs_mesh_count(&g, (float)min_weight, ws.data_ptr(), cur_stream(dev)), "b3gs_mesh_count");
   }
-  return {ws, ws.slice(0, 0, 16).view(at::kLong)};
+  return {ws, head_words(ws, 2)};
 }
 
 // -> (vertices float32 [V, 3], colours uint8 [V, 3], faces int32 [F, 3])
@@ -108,7 +97,7 @@ static std::tuple<Tensor, Tensor, Tensor> mesh_emit(Tensor tsdf, Tensor weight, 
   static const char* what = "mesh_emit";
   B3gsTsdfVolume g = volume_of(tsdf, weight, rgb, origin, voxel, what);
   const at::Device dev = tsdf.device();
-  Tensor ws = mesh_input(workspace, at::kByte, "workspace", &dev);
+  Tensor ws = dev_input(workspace, at::kByte, "workspace", kMeshDeviceOnly, &dev);
   if ((size_t)ws.numel() < b3gs_mesh_workspace_bytes(g.nx, g.ny, g.nz) || !ws.is_contiguous()) throw py::value_error("mesh_emit: the workspace is too small");
   if (nverts < 0 || ntris < 0) throw py::value_error("mesh_emit: negative count");
   if (nverts > INT32_MAX || ntris > INT32_MAX) raise("mesh_emit: the mesh has more than 2^31 - 1 vertices or triangles: use a coarser volume");
@@ -117,8 +106,8 @@ static std::tuple<Tensor, Tensor, Tensor> mesh_emit(Tensor tsdf, Tensor weight, 
   Tensor faces = at::empty({ntris, 3}, opt.dtype(at::kInt));
   {
     DeviceGuard guard(dev);
-    check(b3gs_mesh_emit(&g, ws.data_ptr(), nverts, ntris, nverts ? vertices.data_ptr<float>() : nullptr,
-                         nverts ? colours.data_ptr<uint8_t>() : nullptr, ntris ? faces.data_ptr<int32_t>() : nullptr, cur_stream(dev)),
+    check(b3gs_mesh_emit(&g, ws.data_ptr(), nverts, ntris, ptr_or_null<float>(vertices), ptr_or_null<uint8_t>(colours),
+                         ptr_or_null<int32_t>(faces), cur_stream(dev)),
           "b3gs_mesh_emit");
   }
   return {vertices, colours, faces};

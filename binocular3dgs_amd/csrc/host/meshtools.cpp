@@ -12,23 +12,12 @@ namespace b3 {
 
 static const char* kToolsDeviceOnly = "the mesh tools run on the HIP device only";
 
-// contiguous, of the given type, on the HIP device (and on `dev`)
-static Tensor tool_input(const Tensor& t, at::ScalarType type, const char* name, const at::Device* dev = nullptr) {
-  if (!t.defined() || !t.is_cuda()) raise(std::string(name) + " is on " + (t.defined() ? t.device().str() : "no device") + ": " + kToolsDeviceOnly);
-  if (dev && t.device() != *dev) raise(std::string(name) + " is on " + t.device().str() + ", not on " + dev->str());
-  if (t.scalar_type() != type) throw py::value_error(std::string(name) + ": wrong dtype");
-  return t.contiguous();
-}
 static Tensor rows3(const Tensor& t, at::ScalarType type, const char* name, const at::Device* dev = nullptr) {
-  Tensor r = tool_input(t, type, name, dev);
+  Tensor r = dev_input(t, type, name, kToolsDeviceOnly, dev).contiguous();
   if (r.dim() != 2 || r.size(1) != 3) throw py::value_error(std::string(name) + " is [n, 3]");
   if (r.size(0) > INT32_MAX) throw py::value_error(std::string(name) + ": more than 2^31 - 1 rows");
   return r;
 }
-static Tensor workspace(size_t bytes, const at::Device& dev) {
-  return at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
-}
-static Tensor head_words(const Tensor& ws, int n) { return ws.slice(0, 0, 8 * n).view(at::kLong); }
 
 // faces int32 [F, 3] over V vertices -> (labels int32 [V], tri_count int32 [V])
 static std::tuple<Tensor, Tensor> mesh_components(int64_t V, const Tensor& faces) {
@@ -38,8 +27,8 @@ static std::tuple<Tensor, Tensor> mesh_components(int64_t V, const Tensor& faces
   auto opt = at::TensorOptions().dtype(at::kInt).device(dev);
   Tensor labels = at::empty({V}, opt), count = at::empty({V}, opt);
   DeviceGuard guard(dev);
-  check(b3gs_mesh_components((int32_t)V, f.size(0), f.size(0) ? f.data_ptr<int32_t>() : nullptr, V ? labels.data_ptr<int32_t>() : nullptr,
-                             V ? count.data_ptr<int32_t>() : nullptr, cur_stream(dev)), "b3gs_mesh_components");
+  check(b3gs_mesh_components((int32_t)V, f.size(0), ptr_or_null<int32_t>(f), ptr_or_null<int32_t>(labels), ptr_or_null<int32_t>(count),
+                             cur_stream(dev)), "b3gs_mesh_components");
   return {labels, count};
 }
 
@@ -51,22 +40,20 @@ static CleanIn clean_in(const Tensor& faces, const Tensor& labels, const Tensor&
   CleanIn c;
   c.faces = rows3(faces, at::kInt, "faces");
   const at::Device dev = c.faces.device();
-  c.labels = tool_input(labels, at::kInt, "labels", &dev);
-  c.count = tool_input(tri_count, at::kInt, "tri_count", &dev);
-  c.threshold = tool_input(threshold, at::kInt, "threshold", &dev);
+  c.labels = dev_input(labels, at::kInt, "labels", kToolsDeviceOnly, &dev).contiguous();
+  c.count = dev_input(tri_count, at::kInt, "tri_count", kToolsDeviceOnly, &dev).contiguous();
+  c.threshold = dev_input(threshold, at::kInt, "threshold", kToolsDeviceOnly, &dev).contiguous();
   if (c.labels.dim() != 1 || c.count.sizes() != c.labels.sizes() || c.threshold.numel() != 1)
     throw py::value_error("mesh_clean: labels and tri_count are int32 [V], threshold is one int32");
   c.V = c.labels.size(0), c.F = c.faces.size(0);
   return c;
 }
-template <typename T>
-static T* ptr_or_null(const Tensor& t) { return t.numel() ? t.data_ptr<T>() : nullptr; }
 
 // -> (workspace, totals): int64 [3] {vertices kept, triangles kept, triangles naming no vertex}, on the device
 static std::tuple<Tensor, Tensor> mesh_clean_count(const Tensor& faces, const Tensor& labels, const Tensor& tri_count, const Tensor& threshold) {
   CleanIn c = clean_in(faces, labels, tri_count, threshold);
   const at::Device dev = c.faces.device();
-  Tensor ws = workspace(b3gs_mesh_clean_workspace_bytes(c.V, c.F), dev);
+  Tensor ws = byte_workspace(b3gs_mesh_clean_workspace_bytes(c.V, c.F), dev);
   DeviceGuard guard(dev);
   check(b3gs_mesh_clean_count((int32_t)c.V, c.F, ptr_or_null<int32_t>(c.faces), ptr_or_null<int32_t>(c.labels), ptr_or_null<int32_t>(c.count),
                               c.threshold.data_ptr<int32_t>(), ws.data_ptr(), cur_stream(dev)), "b3gs_mesh_clean_count");
@@ -79,7 +66,7 @@ static std::tuple<Tensor, Tensor, Tensor> mesh_clean_emit(const Tensor& vertices
   CleanIn c = clean_in(faces, labels, tri_count, threshold);
   const at::Device dev = c.faces.device();
   Tensor v = rows3(vertices, at::kFloat, "vertices", &dev), col = rows3(colours, at::kByte, "colours", &dev);
-  Tensor w = tool_input(ws, at::kByte, "workspace", &dev);
+  Tensor w = dev_input(ws, at::kByte, "workspace", kToolsDeviceOnly, &dev).contiguous();
   if (v.size(0) != c.V || col.size(0) != c.V) throw py::value_error("mesh_clean_emit: one vertex and one colour per label");
   if ((size_t)w.numel() < b3gs_mesh_clean_workspace_bytes(c.V, c.F)) throw py::value_error("mesh_clean_emit: the workspace is too small");
   if (nverts < 0 || ntris < 0 || nverts > c.V || ntris > c.F) throw py::value_error("mesh_clean_emit: bad counts");
@@ -100,7 +87,7 @@ static std::tuple<Tensor, Tensor> mesh_sample_count(const Tensor& vertices, cons
   const at::Device dev = v.device();
   Tensor f = rows3(faces, at::kInt, "faces", &dev);
   if (!((float)spacing > 0.f) || !std::isfinite((float)spacing)) throw py::value_error("sample_surface: the spacing is positive and finite");
-  Tensor ws = workspace(b3gs_mesh_sample_workspace_bytes(f.size(0)), dev);
+  Tensor ws = byte_workspace(b3gs_mesh_sample_workspace_bytes(f.size(0)), dev);
   DeviceGuard guard(dev);
   check(b3gs_mesh_sample_count((int32_t)v.size(0), f.size(0), ptr_or_null<float>(v), ptr_or_null<int32_t>(f), (float)spacing, ws.data_ptr(),
                                cur_stream(dev)), "b3gs_mesh_sample_count");
@@ -111,7 +98,7 @@ static Tensor mesh_sample_emit(const Tensor& vertices, const Tensor& faces, doub
   Tensor v = rows3(vertices, at::kFloat, "vertices");
   const at::Device dev = v.device();
   Tensor f = rows3(faces, at::kInt, "faces", &dev);
-  Tensor w = tool_input(ws, at::kByte, "workspace", &dev);
+  Tensor w = dev_input(ws, at::kByte, "workspace", kToolsDeviceOnly, &dev).contiguous();
   if ((size_t)w.numel() < b3gs_mesh_sample_workspace_bytes(f.size(0))) throw py::value_error("sample_surface: the workspace is too small");
   if (npoints < 0 || v.size(0) + npoints > INT32_MAX) throw py::value_error("sample_surface: more than 2^31 - 1 points: use a larger spacing");
   Tensor out = at::empty({v.size(0) + npoints, 3}, at::TensorOptions().dtype(at::kFloat).device(dev));
@@ -131,7 +118,7 @@ static Tensor nearest_grid(const Tensor& b, double max_dist) {
   check_max_dist(max_dist);
   if (pts.size(0) < 1) throw py::value_error("nearest_distances: the cloud searched is empty");
   const at::Device dev = pts.device();
-  Tensor ws = workspace(b3gs_nearest_workspace_bytes(pts.size(0)), dev);
+  Tensor ws = byte_workspace(b3gs_nearest_workspace_bytes(pts.size(0)), dev);
   DeviceGuard guard(dev);
   check(b3gs_nearest_grid(pts.size(0), pts.data_ptr<float>(), (float)max_dist, ws.data_ptr(), cur_stream(dev)), "b3gs_nearest_grid");
   return ws;
@@ -141,7 +128,7 @@ static Tensor nearest_query(const Tensor& a, const Tensor& ws, int64_t nb, doubl
   Tensor q = rows3(a, at::kFloat, "a");
   check_max_dist(max_dist);
   const at::Device dev = q.device();
-  Tensor w = tool_input(ws, at::kByte, "workspace", &dev);
+  Tensor w = dev_input(ws, at::kByte, "workspace", kToolsDeviceOnly, &dev).contiguous();
   if (nb < 1 || nb > INT32_MAX || (size_t)w.numel() < b3gs_nearest_workspace_bytes(nb)) throw py::value_error("nearest_distances: the workspace is too small");
   Tensor out = at::empty({q.size(0)}, at::TensorOptions().dtype(at::kFloat).device(dev));
   DeviceGuard guard(dev);
@@ -152,17 +139,17 @@ static Tensor nearest_query(const Tensor& a, const Tensor& ws, int64_t nb, doubl
 
 // dist float32 [N], mask bool [N] or None -> out (float64 [3] on the device, written): sum, count, count below tau
 static void cloud_score(const Tensor& dist, const c10::optional<Tensor>& mask, double tau, Tensor out) {
-  Tensor d = tool_input(dist, at::kFloat, "dist");
+  Tensor d = dev_input(dist, at::kFloat, "dist", kToolsDeviceOnly).contiguous();
   const at::Device dev = d.device();
   if (d.dim() != 1 || d.size(0) < 1 || d.size(0) > INT32_MAX) throw py::value_error("cloud_score: dist is float32 [N], 1 <= N <= 2^31 - 1");
   Tensor m;
   if (mask.has_value()) {
-    m = tool_input(*mask, at::kBool, "mask", &dev);
+    m = dev_input(*mask, at::kBool, "mask", kToolsDeviceOnly, &dev).contiguous();
     if (m.dim() != 1 || m.size(0) != d.size(0)) throw py::value_error("cloud_score: one mask value per point");
   }
   if (!out.defined() || !out.is_cuda() || out.device() != dev || out.scalar_type() != at::kDouble || out.numel() != 3 || !out.is_contiguous())
     throw py::value_error("cloud_score: out is a contiguous float64 [3] on the device of dist");
-  Tensor ws = workspace(b3gs_cloud_score_workspace_bytes(d.size(0)), dev);
+  Tensor ws = byte_workspace(b3gs_cloud_score_workspace_bytes(d.size(0)), dev);
   DeviceGuard guard(dev);
   check(b3gs_cloud_score(d.size(0), d.data_ptr<float>(), m.defined() ? reinterpret_cast<const uint8_t*>(m.data_ptr<bool>()) : nullptr, (float)tau,
                          out.data_ptr<double>(), ws.data_ptr(), cur_stream(dev)), "b3gs_cloud_score");

@@ -11,24 +11,18 @@ namespace b3 {
 
 static const char* kSweepDeviceOnly = "the sweep matcher runs on the HIP device only";
 
-static Tensor sweep_input(const Tensor& t, at::ScalarType type, const char* name, const at::Device* dev = nullptr) {
-  if (!t.defined() || !t.is_cuda()) raise(std::string(name) + " is on " + (t.defined() ? t.device().str() : "no device") + ": " + kSweepDeviceOnly);
-  if (dev && t.device() != *dev) raise(std::string(name) + " is on " + t.device().str() + ", not on " + dev->str());
-  if (t.scalar_type() != type) throw py::value_error(std::string(name) + ": wrong dtype");
-  return t.is_contiguous() ? t : t.contiguous();
-}
-
 // -> (kp_source [2,nodes,2], kp_target [2,nodes,2], score [2,nodes], count int32 [2], node_invd [2,nodes], node_score [2,nodes],
 //     node_k int32 [2,nodes]); rows [0, count[d]) of direction d (0: a -> b, 1: b -> a) are the kept matches in node order
 static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> sweep_match_pair(
     const Tensor& image_a, const Tensor& image_b, const Tensor& homographies, const Tensor& proj, double near, double far, double inv_far,
     double step, int64_t stride, int64_t radius, double min_score, double margin, double min_var, double cyc_steps) {
-  Tensor ia = sweep_input(image_a, at::kByte, "sweep_match_pair: image_a");
+  Tensor ia = dev_input(image_a, at::kByte, "sweep_match_pair: image_a", kSweepDeviceOnly).contiguous();
   const at::Device dev = ia.device();
-  Tensor ib = sweep_input(image_b, at::kByte, "sweep_match_pair: image_b", &dev);
+  Tensor ib = dev_input(image_b, at::kByte, "sweep_match_pair: image_b", kSweepDeviceOnly, &dev).contiguous();
   if (ia.dim() != 3 || ia.size(2) != 3 || ib.dim() != 3 || ib.sizes() != ia.sizes())
     throw py::value_error("sweep_match_pair: image_a and image_b are uint8 [H, W, 3] images of one size");
-  Tensor hs = sweep_input(homographies, at::kFloat, "homographies", &dev), pj = sweep_input(proj, at::kFloat, "proj", &dev);
+  Tensor hs = dev_input(homographies, at::kFloat, "homographies", kSweepDeviceOnly, &dev).contiguous();
+  Tensor pj = dev_input(proj, at::kFloat, "proj", kSweepDeviceOnly, &dev).contiguous();
   if (hs.dim() != 4 || hs.size(0) != 2 || hs.size(2) != 3 || hs.size(3) != 3) throw py::value_error("sweep_match_pair: homographies is float32 [2, D, 3, 3]");
   if (pj.dim() != 2 || pj.size(0) != 2 || pj.size(1) != 12) throw py::value_error("sweep_match_pair: proj is float32 [2, 12]");
   const int64_t H = ia.size(0), W = ia.size(1), D = hs.size(1);
@@ -42,7 +36,7 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> sweep_
   Tensor kp_source = at::empty({2, nodes, 2}, f32), kp_target = at::empty({2, nodes, 2}, f32), score = at::empty({2, nodes}, f32);
   Tensor count = at::empty({2}, i32);
   Tensor node_invd = at::empty({2, nodes}, f32), node_score = at::empty({2, nodes}, f32), node_k = at::empty({2, nodes}, i32);
-  Tensor ws = at::empty({(int64_t)bytes}, f32.dtype(at::kByte));
+  Tensor ws = byte_workspace(bytes, dev);
   B3gsSweepPair io = {};
   io.W = (int32_t)W;
   io.H = (int32_t)H;

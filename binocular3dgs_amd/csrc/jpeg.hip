@@ -237,12 +237,6 @@ __device__ __forceinline__ int prev_dc(const int16_t* mc, int m, int b) {
   return mc[-MCU_COEFS + (b == 0 ? 3 : b) * 64];
 }
 
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
 // grid (ceil(nm / 4), nv)
 __global__ void __launch_bounds__(TPB) jpeg_size_kernel(int nm, JpegWork w) {
   __shared__ uint32_t hs[HUFF_WORDS];
@@ -259,36 +253,13 @@ __global__ void __launch_bounds__(TPB) jpeg_size_kernel(int nm, JpegWork w) {
     lane_code(mc[b * 64 + lane], lane, b >> 2, lane == 0 ? prev_dc(mc, m, b) : 0, hs, val, len);
     bits += len;
   }
-  bits = wave_sum(bits);
+  bits = b3gs_wave_sum(bits);
   if (lane == 0) w.mbits[(size_t)v * nm + m] = (uint32_t)bits;
-}
-
-// exclusive scan over the workgroup (SCAN_TPB threads); *total = the sum.  Safe to call in a loop.
-__device__ unsigned long long block_scan(unsigned long long x, unsigned long long* total) {
-  __shared__ unsigned long long ws[SCAN_TPB / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long inc = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long y = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += y;
-  }
-  __syncthreads();
-  if (lane == 63) ws[wave] = inc;
-  __syncthreads();
-  unsigned long long before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < SCAN_TPB / 64; k++) {
-    const unsigned long long s = ws[k];
-    if (k < wave) before += s;
-    all += s;
-  }
-  *total = all;
-  return before + inc - x;
 }
 
 // grid (nv): bit offsets of the MCUs; zeroes the words of the scan (whole 64-byte chunks)
 __global__ void __launch_bounds__(SCAN_TPB) jpeg_scan_kernel(int nm, JpegWork w) {
+  __shared__ unsigned long long wave_n[SCAN_TPB / B3GS_WAVE];
   const int v = blockIdx.x;
   const uint32_t* __restrict__ mb = w.mbits + (size_t)v * nm;
   unsigned long long* __restrict__ mo = w.moff + (size_t)v * nm;
@@ -296,7 +267,7 @@ __global__ void __launch_bounds__(SCAN_TPB) jpeg_scan_kernel(int nm, JpegWork w)
   for (int base = 0; base < nm; base += SCAN_TPB) {
     const int i = base + (int)threadIdx.x;
     unsigned long long tile;
-    const unsigned long long ex = block_scan(i < nm ? mb[i] : 0u, &tile);
+    const unsigned long long ex = b3gs_block_exscan<SCAN_TPB>((unsigned long long)(i < nm ? mb[i] : 0u), wave_n, &tile);
     if (i < nm) mo[i] = carry + ex;
     carry += tile;
   }
@@ -338,12 +309,7 @@ __global__ void __launch_bounds__(TPB) jpeg_emit_kernel(int nm, JpegWork w) {
     unsigned long long val;
     int len;
     lane_code(mc[b * 64 + lane], lane, b >> 2, lane == 0 ? prev_dc(mc, m, b) : 0, hs, val, len);
-    int inc = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int y = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += y;
-    }
+    const int inc = b3gs_wave_scan(len, lane);
     if (len) put_bits(words, w.words_per_view, off + (unsigned long long)(inc - len), val, len);
     off += (unsigned long long)__shfl(inc, 63, 64);
   }
@@ -358,6 +324,7 @@ __device__ __forceinline__ uint32_t stream_byte(uint32_t word, int k) { return (
 
 // grid (nv): 0xFF bytes before every chunk; lengths[v] = bytes of the stuffed scan, or -1 when they exceed the capacity
 __global__ void __launch_bounds__(SCAN_TPB) jpeg_stuffscan_kernel(JpegWork w, long long capacity, long long* __restrict__ lengths) {
+  __shared__ unsigned long long wave_n[SCAN_TPB / B3GS_WAVE];
   const int v = blockIdx.x;
   const unsigned long long nbytes = w.tot[2 * v + 1];
   const size_t nchunks = (size_t)((nbytes + CHUNK - 1) / CHUNK);
@@ -381,7 +348,7 @@ __global__ void __launch_bounds__(SCAN_TPB) jpeg_stuffscan_kernel(JpegWork w, lo
       }
     }
     unsigned long long tile;
-    const unsigned long long ex = block_scan(n, &tile);
+    const unsigned long long ex = b3gs_block_exscan<SCAN_TPB>((unsigned long long)n, wave_n, &tile);
     if (c < nchunks) fo[c] = carry + ex;
     carry += tile;
   }

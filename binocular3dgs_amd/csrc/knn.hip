@@ -19,18 +19,8 @@ __global__ void __launch_bounds__(256) bbox_partial_kernel(int P, const float* _
   for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256)
 #pragma unroll
     for (int a = 0; a < 3; a++) { const float v = pts[3 * (size_t)i + a]; lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v); }
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64)); }
-  if ((threadIdx.x & 63) == 0)
-    for (int a = 0; a < 3; a++) { red[threadIdx.x >> 6][a] = lo[a]; red[threadIdx.x >> 6][3 + a] = hi[a]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float v = red[0][threadIdx.x];
-    for (int w = 1; w < 4; w++) v = threadIdx.x < 3 ? fminf(v, red[w][threadIdx.x]) : fmaxf(v, red[w][threadIdx.x]);
-    part[blockIdx.x * 6 + threadIdx.x] = v;
-  }
+  const float v = b3gs_block_bbox<256>(lo, hi, red);
+  if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = v;
 }
 
 __device__ __forceinline__ uint32_t spread10(uint32_t x) {
@@ -74,18 +64,9 @@ __global__ void __launch_bounds__(KNN_BOX) box_kernel(int P, const float* __rest
 #pragma unroll
     for (int a = 0; a < 3; a++) { const float v = pts[3 * (size_t)src + a]; sorted[3 * (size_t)i + a] = v; lo[a] = hi[a] = v; }
   }
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64)); }
-  if ((threadIdx.x & 63) == 0)
-    for (int a = 0; a < 3; a++) { red[threadIdx.x >> 6][a] = lo[a]; red[threadIdx.x >> 6][3 + a] = hi[a]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float v = red[0][threadIdx.x];
-    for (int w = 1; w < KNN_BOX / 64; w++) v = threadIdx.x < 3 ? fminf(v, red[w][threadIdx.x]) : fmaxf(v, red[w][threadIdx.x]);
-    if (threadIdx.x < 3) boxes[blockIdx.x].lo[threadIdx.x] = v; else boxes[blockIdx.x].hi[threadIdx.x - 3] = v;
-  }
+  const float v = b3gs_block_bbox<KNN_BOX>(lo, hi, red);
+  if (threadIdx.x < 3) boxes[blockIdx.x].lo[threadIdx.x] = v;
+  else if (threadIdx.x < 6) boxes[blockIdx.x].hi[threadIdx.x - 3] = v;
 }
 
 __device__ __forceinline__ void insert3(float d, float (&best)[3]) {

@@ -264,9 +264,7 @@ __global__ void __launch_bounds__(TPB) sample_count_kernel(SampleArgs a) {
     }
     a.nn[t] = code;
   }
-  unsigned long long wide = cnt;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) wide += __shfl_xor(wide, d, 64);
+  const unsigned long long wide = b3gs_wave_sum((unsigned long long)cnt);
   if ((threadIdx.x & 63) == 0 && wide) atomicAdd(reinterpret_cast<unsigned long long*>(a.totals), wide);
   uint32_t total;
   b3gs_block_exscan<TPB>(cnt, wave_n, &total);
@@ -367,18 +365,8 @@ __global__ void __launch_bounds__(TPB) near_bbox_kernel(int32_t n, const float* 
   for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB)
 #pragma unroll
     for (int a = 0; a < 3; a++) { const float v = pts[3 * i + a]; lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v); }
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64)); }
-  if ((threadIdx.x & 63) == 0)
-    for (int a = 0; a < 3; a++) { red[threadIdx.x >> 6][a] = lo[a]; red[threadIdx.x >> 6][3 + a] = hi[a]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float v = red[0][threadIdx.x];
-    for (int w = 1; w < TPB / 64; w++) v = threadIdx.x < 3 ? fminf(v, red[w][threadIdx.x]) : fmaxf(v, red[w][threadIdx.x]);
-    part[blockIdx.x * 6 + threadIdx.x] = v;
-  }
+  const float v = b3gs_block_bbox<TPB>(lo, hi, red);
+  if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = v;
 }
 
 // the cell coordinate of x along one axis, before clamping: one function for points and queries, monotone in x
@@ -510,12 +498,6 @@ static int score_blocks(int64_t n) {
   return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ void __launch_bounds__(TPB) score_partial_kernel(int64_t n, const float* __restrict__ dist, const uint8_t* __restrict__ mask,
                                                             float tau, int nb, double* __restrict__ part) {
   double q[SCORE_Q] = {0.0, 0.0, 0.0};
@@ -527,24 +509,13 @@ __global__ void __launch_bounds__(TPB) score_partial_kernel(int64_t n, const flo
     if (d < tau) q[2] += 1.0;
   }
   __shared__ double red[TPB / 64][SCORE_Q];
-#pragma unroll
-  for (int k = 0; k < SCORE_Q; k++) {
-    const double s = wave_sum(q[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < SCORE_Q) {
-    const int k = threadIdx.x;
-    part[(size_t)blockIdx.x * SCORE_Q + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-  }
+  b3gs_block_sum_f64<TPB>(q, red, part + (size_t)blockIdx.x * SCORE_Q);
 }
 
 // one wave: fixed assignment of partials to lanes, fixed tree
 __global__ void __launch_bounds__(64) score_fold_kernel(const double* __restrict__ part, int nb, double* __restrict__ out) {
   for (int k = 0; k < SCORE_Q; k++) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 64) s += part[(size_t)b * SCORE_Q + k];
-    s = wave_sum(s);
+    const double s = b3gs_wave_fold_f64(part + k, nb, SCORE_Q);
     if (threadIdx.x == 0) out[k] = s;
   }
 }

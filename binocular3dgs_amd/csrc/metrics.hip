@@ -44,12 +44,6 @@ __device__ __forceinline__ float prepare(float x, int mode) {
   return x;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 // grid (bpv, views of this chunk): workgroup b of view v walks pixels b*256 + tid, stride bpv*256, all channels of a pixel
 // in one thread; it leaves NQ partial sums at part[(view0 + v) * bpv + b]
 __global__ void __launch_bounds__(TPB) metrics_partial_kernel(MetricTable t, int C, int64_t hw, int mode, int view0, int bpv,
@@ -93,7 +87,6 @@ __global__ void __launch_bounds__(TPB) metrics_partial_kernel(MetricTable t, int
     }
   }
   __shared__ double red[TPB / 64][NQ];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double q[NQ];
 #pragma unroll
   for (int c = 0; c < MC; c++) {
@@ -102,16 +95,7 @@ __global__ void __launch_bounds__(TPB) metrics_partial_kernel(MetricTable t, int
   }
   q[2 * MC] = sm;
   q[2 * MC + 1] = cnt;
-#pragma unroll
-  for (int k = 0; k < NQ; k++) {
-    const double s = wave_sum(q[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NQ) {
-    const int k = threadIdx.x;
-    part[((int64_t)(view0 + v) * bpv + blockIdx.x) * NQ + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-  }
+  b3gs_block_sum_f64<TPB>(q, red, part + ((int64_t)(view0 + v) * bpv + blockIdx.x) * NQ);
 }
 
 // one wave per view: fixed assignment of partials to lanes, fixed tree -> out[v, 2C + 2]
@@ -122,9 +106,7 @@ __global__ void __launch_bounds__(64) metrics_fold_kernel(const double* __restri
   for (int k = 0; k < nq; k++) {
     // output k of the ABI row -> partial slot: Σ|d| channels 0..C-1, Σd² channels 0..C-1, masked Σd², count
     const int slot = k < C ? k : (k < 2 * C ? MC + (k - C) : 2 * MC + (k - 2 * C));
-    double a = 0.0;
-    for (int b = threadIdx.x; b < bpv; b += 64) a += part[((int64_t)v * bpv + b) * NQ + slot];
-    a = wave_sum(a);
+    const double a = b3gs_wave_fold_f64(part + (int64_t)v * bpv * NQ + slot, bpv, NQ);
     if (threadIdx.x == 0) out[(int64_t)v * nq + k] = a;
   }
 }

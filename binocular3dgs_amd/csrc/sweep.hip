@@ -177,42 +177,14 @@ __global__ void __launch_bounds__(CTPB) check_kernel(Args a) {
     }
     a.keep[(size_t)dir * a.n + node] = keep ? 1 : 0;
   }
-  const unsigned long long b = __ballot(keep);
-  if ((threadIdx.x & (B3GS_WAVE - 1)) == 0) wave_n[threadIdx.x / B3GS_WAVE] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < CTPB / B3GS_WAVE; w++) s += wave_n[w];
-    a.block_count[(size_t)dir * (a.nb + 1) + blockIdx.x] = s;
-  }
+  int total;
+  b3gs_block_rank<CTPB, 1>(keep, wave_n, &total);
+  if (threadIdx.x == 0) a.block_count[(size_t)dir * (a.nb + 1) + blockIdx.x] = total;
 }
 
 // one block per direction: exclusive scan of the block counts in place, the total to count[dir]
-__global__ void __launch_bounds__(1024) scan_kernel(Args a) {
-  __shared__ int wave_n[16];
-  __shared__ int carry;
-  int32_t* block_count = a.block_count + (size_t)blockIdx.x * (a.nb + 1);
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int b0 = 0; b0 < a.nb; b0 += 1024) {
-    const int b = b0 + threadIdx.x;
-    const int v = b < a.nb ? block_count[b] : 0;
-    int incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_n[wv] = incl;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wv; w++) before += wave_n[w];
-    if (b < a.nb) block_count[b] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.io.count[blockIdx.x] = carry;
+__global__ void __launch_bounds__(B3GS_SCAN_TPB) scan_kernel(Args a) {
+  b3gs_scan_block_sums(a.block_count + (size_t)blockIdx.x * (a.nb + 1), a.nb, a.io.count + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(CTPB) compact_kernel(Args a) {
@@ -221,13 +193,9 @@ __global__ void __launch_bounds__(CTPB) compact_kernel(Args a) {
   const int dir = blockIdx.y;
   const int node = blockIdx.x * CTPB + threadIdx.x;
   const bool keep = node < a.n && a.keep[(size_t)dir * a.n + node] != 0;
-  const unsigned long long b = __ballot(keep);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) wave_n[wv] = __popcll(b);
-  __syncthreads();
+  int total;
+  const int slot = a.block_count[(size_t)dir * (a.nb + 1) + blockIdx.x] + b3gs_block_rank<CTPB, 1>(keep, wave_n, &total);
   if (!keep) return;
-  int slot = a.block_count[(size_t)dir * (a.nb + 1) + blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wv; w++) slot += wave_n[w];
   if (slot >= a.n) return;                                                          // (cannot happen: the outputs hold n rows)
   const size_t o = (size_t)dir * a.n + slot, in = (size_t)dir * a.n + node;
   g.kp_source[2 * o] = (float)(RADIUS + (node % a.nx) * g.stride);
@@ -291,7 +259,7 @@ extern "C" int b3gs_sweep_match_pair(const B3gsSweepPair* io, b3gs_stream_t stre
   hipLaunchKernelGGL(gray_kernel, dim3((unsigned)((g.W * g.H + CTPB - 1) / CTPB), 2), dim3(CTPB), 0, s, a);
   hipLaunchKernelGGL(score_kernel, dim3((unsigned)((l.n + TPB - 1) / TPB), 2), dim3(TPB), 0, s, a);
   hipLaunchKernelGGL(check_kernel, dim3((unsigned)l.nb, 2), dim3(CTPB), 0, s, a);
-  hipLaunchKernelGGL(scan_kernel, dim3(2), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(scan_kernel, dim3(2), dim3(B3GS_SCAN_TPB), 0, s, a);
   hipLaunchKernelGGL(compact_kernel, dim3((unsigned)l.nb, 2), dim3(CTPB), 0, s, a);
   return b3gs_launch_status(what);
 }

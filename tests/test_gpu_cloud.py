@@ -93,6 +93,36 @@ def test_background_sheet(g):
     assert np.abs(pts.cpu().numpy() - f64).max() < 1e-4
 
 
+def test_background_sheet_across_the_seam_of_the_block_scan():
+    """520 x 512 pixels are 1040 blocks of 256: two steps of the 1024-wide scan of the block counts.  The count and every row,
+    in pixel order, against the float64 restatement.  Bound: a coordinate goes through about 20 float32 roundings on the device
+    and two float32 matrix inversions on the host, each 2^-24 of a value no larger than scale = depth (W / fx + H / fy + 1) +
+    |t|; 64 * 2^-24 * scale (1.2e-4 here) covers them.  Neighbouring pixels' points lie depth / fx = 0.02 apart, 160 times
+    that, so a row out of order cannot pass."""
+    from binocular3dgs_amd import matcher_cloud as mc
+    W, H, depth = 520, 512, 10.0
+    K = np.array([[500.0, 0, 260.0], [0, 500.0, 256.0], [0, 0, 1]], np.float32)
+    c2w = np.eye(4, dtype=np.float32)
+    c2w[:3, :3] = [[0.8, 0.0, 0.6], [0.0, 1.0, 0.0], [-0.6, 0.0, 0.8]]
+    c2w[:3, 3] = [1.0, -2.0, 0.5]
+    rng = np.random.default_rng(5)
+    img = rng.integers(0, 254, (H, W, 3), dtype=np.uint8)
+    # white pixels at a density that changes from row to row (block counts from 0 to 256), 254 and 255 both
+    white = rng.random((H, W)) < np.linspace(0.0, 1.0, H)[:, None] ** 2
+    white[200:203] = True
+    white[300:303] = False
+    img[white, rng.integers(0, 3, int(white.sum()))] = rng.integers(254, 256, int(white.sum()), dtype=np.uint8)
+    mask = (img.max(axis=2) >= 254).ravel()
+    assert np.array_equal(mask, white.ravel()) and 0.2 < mask.mean() < 0.5
+    pts, col = mc.background_sheet(img, K, c2w, depth, device=DEV)
+    assert len(pts) == int(mask.sum()) and (col.cpu().numpy() == 255).all()
+    want = cloud_ref.sheet_points_f64(W, H, K, c2w, depth)[mask]
+    scale = depth * (W / 500.0 + H / 500.0 + 1.0) + float(np.abs(c2w[:3, 3]).max())
+    err = float(np.abs(pts.cpu().numpy() - want).max())
+    print("sheet across the seam: kept", len(pts), "max |point - float64| =", err, "bound", 64 * 2.0 ** -24 * scale)
+    assert err <= 64 * 2.0 ** -24 * scale
+
+
 def _grower(g, capacity=None):
     from binocular3dgs_amd import matcher_cloud as mc
     refs = g["grow/ref_indices"].tolist()

@@ -56,6 +56,21 @@ def test_scan_bytes_equal_the_yardstick(name, quality, W, H):
     assert data == J.encode(img, quality)
 
 
+def test_scan_bytes_across_the_seam_of_the_looped_scans():
+    """528 x 512 is 33 x 32 = 1056 MCUs: two trips of the 1024-thread scan of the MCU bit counts.  Noise at quality 100 gives more
+    than 64 KiB of scan (1024 chunks of 64 bytes), so the scan of the stuffed bytes loops as well, with stuffed bytes in every
+    trip."""
+    W, H, quality = 528, 512, 100
+    img = J.GENERATORS["noise"](W, H, seed=3)
+    st = {}
+    ref = J.scan(img, quality, st)
+    assert st["blocks"] == 6 * 1056 and len(ref) > 2 * 1024 * 64 and st["stuffed"] > 0
+    lengths, out = _scans([img], quality, canary=0x5A)
+    assert lengths == [len(ref)]
+    assert out[0, :len(ref)].tobytes() == ref
+    assert (out[0, len(ref):] == 0x5A).all()
+
+
 @pytest.mark.parametrize("n", [1, 3, 8])
 def test_batches_of_different_views(n):
     W, H = 40, 24

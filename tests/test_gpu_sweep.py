@@ -165,6 +165,28 @@ def test_shapes_where_indexing_can_go_wrong(W, H, stride, D):
         assert ties / 2 <= 0.02
 
 
+def test_kept_matches_across_the_seam_of_the_block_scan():
+    """520 x 520 at stride 1: 514 x 514 = 264 196 nodes per direction, 1033 compaction blocks of 256 -- two steps of the 1024-wide
+    scan of the block counts, in both directions (rows of nb + 1 words).  D = 2, the fewest hypotheses the call takes.  Compared
+    as the shapes above are, with the same allowance for ties."""
+    W = H = 520
+    sc = sr.make_scene(W=W, H=H, baseline=0.1 * W / 96.0)      # a short baseline: both views keep matches in their last rows
+    imgs = [sr.render(sc, v) for v in range(2)]
+    p = sr.Params(stride=1, hypotheses=2)
+    xs, ys = sr.node_axes(W, H, 1)
+    assert len(xs) * len(ys) == 264196 and (len(xs) * len(ys) + 255) // 256 == 1033
+    wants, err32 = _restated(sc, imgs, 0, 1, p)
+    out = _launch(imgs[0], imgs[1], sc.K, sc.c2ws[0], sc.c2ws[1], sc.near, sc.far, p)
+    assert out[0].shape == (2, len(xs) * len(ys), 2)
+    ties = 0
+    for d in range(2):
+        share, n, kept = _compare(out, wants[d], d, W, H, p, err32, f"{W}x{H} stride 1 D 2 dir {d}")
+        ties += share
+        assert wants[d]["keep"][:1024 * 256].any() and wants[d]["keep"][1024 * 256:].any()    # the yardstick keeps nodes on both
+        assert 0 < n < len(kept) and kept[:1024 * 256].any() and kept[1024 * 256:].any()      # sides of the seam, and so does the kernel
+    assert ties / 2 <= 0.02
+
+
 def test_a_pair_that_looks_away_has_no_matches():
     from binocular3dgs_amd import sweep_matcher as sm
     sc = sr.make_scene(W=50, H=37)
