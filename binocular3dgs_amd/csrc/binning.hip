@@ -1020,7 +1020,7 @@ void radix9_pass(SortBatch& sb, int shift, bool xform, hipStream_t s) {
   else radix9_pass_t<16>(sb, shift, xform, s);
 }
 
-// one pass over all jobs; swaps every job's in/out buffers afterwards (vin becomes non-null)
+// one pass over all jobs (radix_pass below); it leaves the jobs as they are: the CALLER swaps in / out before the next pass
 template <int BITS>
 void launch_scatter(const SortBatch& sb, bool any_val, uint32_t max_blk, int shift, hipStream_t s) {
   if (any_val) hipLaunchKernelGGL((radix_scatter<true, BITS>), dim3(B3GS_SORT_GRID_X(max_blk), sb.n), dim3(B3GS_SORT_THREADS), 0, s, sb, shift);
@@ -1563,15 +1563,43 @@ int tile_sort_passes(int W, int H) {
 
 }  // namespace
 
+// ---- small host helpers of the launchers below ---------------------------------------------------------------------
+// the tile rects of a job as the projection wrote them, and their stride in elements
+struct RectRef { const uint2* ptr; int32_t stride; };
+static RectRef rect_of(const BinJob& jb) { return jb.rect ? RectRef{jb.rect, jb.rect_stride} : RectRef{jb.g.rect, 1}; }
+
+// n_bound for the scans' overflow test: clamped to 32 bits ...
+static uint32_t bound32(const BinJob& jb) {
+  return (uint32_t)(jb.n_bound > 0 ? (jb.n_bound < 0xFFFFFFFFll ? jb.n_bound : 0xFFFFFFFFll) : 0);
+}
+// ... and as the instance capacity n_cap of the emission and the tile split: the plain cast (the two differ from 2^32 on)
+static uint32_t cap32(const BinJob& jb) { return (uint32_t)(jb.n_bound > 0 ? jb.n_bound : 0); }
+
+// how a scan over `count` > 0 Gaussians of the depth order is chunked: 4096-Gaussian tiles, at most SCAN_MAX_CHUNKS chunks
+struct ScanChunks { int32_t tiles_per_chunk, nchunks; };
+static ScanChunks scan_chunks(int32_t count) {
+  const int total_tiles = (count + SCAN_TILE - 1) / SCAN_TILE;
+  const int per = (total_tiles + SCAN_MAX_CHUNKS - 1) / SCAN_MAX_CHUNKS;
+  return ScanChunks{per, (total_tiles + per - 1) / per};
+}
+
+// after a pass: what it wrote is the next pass's input, what it read the next output
+static void swap_in_out(SortBatch& sb) {
+  for (int k = 0; k < sb.n; k++) {
+    SortJob& j = sb.j[k];
+    const uint32_t* kin = j.kin; const uint32_t* vin = j.vin;
+    j.kin = j.kout; j.vin = j.vout;
+    j.kout = const_cast<uint32_t*>(kin); j.vout = const_cast<uint32_t*>(vin);  // stays null for packed keys
+  }
+}
+
 // the view whose rects sit in the odd slots of view d's [P][2] rect array and which borrows d's depth order: d's scan
 // workgroups gather both rects with one load and keep ONE flagged list for the pair (or -1)
 static int scan_partner_of(const BinJob* jobs, int nviews, int d) {
-  const uint2* rd = jobs[d].rect ? jobs[d].rect : jobs[d].g.rect;
-  const int sd = jobs[d].rect ? jobs[d].rect_stride : 1;
+  const RectRef rd = rect_of(jobs[d]);
   for (int v = 0; v < nviews; v++) {
-    const uint2* rv = jobs[v].rect ? jobs[v].rect : jobs[v].g.rect;
-    const int sv = jobs[v].rect ? jobs[v].rect_stride : 1;
-    if (jobs[v].order_from == d && sv == 2 && sd == 2 && rv == rd + 1) return v;
+    const RectRef rv = rect_of(jobs[v]);
+    if (jobs[v].order_from == d && rv.stride == 2 && rd.stride == 2 && rv.ptr == rd.ptr + 1) return v;
   }
   return -1;
 }
@@ -1648,6 +1676,7 @@ void b3gs_launch_depth_order_batch(int32_t P, int nviews, const BinJob* jobs, hi
   for (int pass = 0; pass < npass; pass++) {
     if (span27) radix9_pass(db, 9 * pass, pass == 0, s);
     else radix_pass(db, 8 * pass, s);
+    // (not swap_in_out: the first pass reads depth_key, which no pass may overwrite)
     for (int k = 0; k < db.n; k++) {
       const GeomView& g = jobs[sorted_view[k]].g;
       const int src = (first_dst + pass) & 1;   // where this pass wrote: the next one reads it and writes the other
@@ -1662,13 +1691,13 @@ void b3gs_launch_depth_order_batch(int32_t P, int nviews, const BinJob* jobs, hi
     hipLaunchKernelGGL(adopt_order_kernel, dim3((P + 1023) / 1024, adopt.n), dim3(256), 0, s, adopt);
 
   // ---- 2. scan of tiles_touched in depth order -> soffs, N, V (segment 1 = the first K1 Gaussians of the order)
-  const int total_tiles = (P + SCAN_TILE - 1) / SCAN_TILE;
+  const ScanChunks ch = scan_chunks(P);
   ScanBatch sc;
   sc.n = nviews;
   sc.P = P;
   sc.K1 = K1;
-  sc.tiles_per_chunk = (total_tiles + SCAN_MAX_CHUNKS - 1) / SCAN_MAX_CHUNKS;
-  sc.nchunks = (total_tiles + sc.tiles_per_chunk - 1) / sc.tiles_per_chunk;
+  sc.tiles_per_chunk = ch.tiles_per_chunk;
+  sc.nchunks = ch.nchunks;
   sc.repair_barrier = (K1 < P && jobs[0].im.header) ? jobs[0].im.header + B3GS_HDR_REPAIR_BARRIER : nullptr;
   if (sc.tiles_per_chunk * SCAN_ITEMS > SCAN_MAX_SUBS) {   // LDS sub-block sums of scan_chunk_sums (P < 2^24 keeps it at 32)
     (void)b3gs_fail(B3GS_ERR_ARG, "b3gs_launch_depth_order_batch", "too many Gaussians for the scan's sub-block table");
@@ -1676,13 +1705,11 @@ void b3gs_launch_depth_order_batch(int32_t P, int nviews, const BinJob* jobs, hi
   }
   for (int v = 0; v < nviews; v++) {
     const BinJob& jb = jobs[v];
-    const uint2* rect = jb.rect ? jb.rect : jb.g.rect;
-    const int32_t rstride = jb.rect ? jb.rect_stride : 1;
-    sc.j[v] = ScanJob{depth_order_of(jobs, v), rect, rstride, -1, jb.g.srect, jb.g.soffs, jb.g.scan_tmp,
+    const RectRef rect = rect_of(jb);
+    sc.j[v] = ScanJob{depth_order_of(jobs, v), rect.ptr, rect.stride, -1, jb.g.srect, jb.g.soffs, jb.g.scan_tmp,
                       reinterpret_cast<uint4*>(jb.g.scan_tmp + SCAN_MAX_CHUNKS), reinterpret_cast<uint4*>(jb.g.scan_tmp + 5 * SCAN_MAX_CHUNKS),
                       jb.g.header, jb.im.header, jb.n_out, jb.g.scount,
-                      open_map(jb.im.pred_rows, jb.W, jb.H), jb.high_water, jb.overflow_flag,
-                      (uint32_t)(jb.n_bound > 0 ? (jb.n_bound < 0xFFFFFFFFll ? jb.n_bound : 0xFFFFFFFFll) : 0), jb.g.pflag,
+                      open_map(jb.im.pred_rows, jb.W, jb.H), jb.high_water, jb.overflow_flag, bound32(jb), jb.g.pflag,
                       jb.g.flist, jb.g.fcount, jb.g.tsum, (K1 < P && jb.order_from == -1) ? 1 : 0};
   }
   // a view that borrows view d's depth order AND whose rects sit in the odd slots of d's [P][2] array is folded
@@ -1701,6 +1728,74 @@ void b3gs_launch_depth_order_batch(int32_t P, int nviews, const BinJob* jobs, hi
   // (no per-Gaussian offsets: the emission scans inside its 256-Gaussian sub-block, see scan_chunk_sums)
 }
 
+// ---- the tile lists of one round: emission in depth order, stable split by tile id, per-tile ranges --------------------
+// Both rounds run these stages on the same ping-pong arrays, from the job tables of build_tile_list_jobs: round 1
+// (b3gs_launch_tile_lists_batch) bins the nearest K1 Gaussians everywhere and the rest into the tiles predicted open; round 2
+// (b3gs_launch_round2_batch) puts the rest into the tiles that segment 1 left open, BEHIND segment 1 in the same arrays.
+struct TileListDims { uint32_t max_cap; int tbits; };   // largest instance capacity (0: nothing to launch), widest tile id
+// fills eb.j[v], tb.j[v] and rb.j[v] (tb for pass 0: build_tile_split steps it on); every view has the tile-sort depth of
+// view 0.  The passes ping-pong between [first] and [first ^ 1] so that the lists end in [0], where the blend expects them.
+static TileListDims build_tile_list_jobs(const BinJob* jobs, int nviews, int32_t P, int round, EmitBatch& eb, SortBatch& tb,
+                                         RangeBatch& rb) {
+  const int first = tile_sort_passes(jobs[0].W, jobs[0].H) & 1;
+  const bool r2 = round == 2;
+  TileListDims d{0, 0};
+  tb.n = rb.n = nviews;
+  for (int v = 0; v < nviews; v++) {
+    const BinJob& jb = jobs[v];
+    d.tbits = max(d.tbits, b3gs_tile_bits(jb.W, jb.H));
+    const uint32_t n_cap = cap32(jb);
+    d.max_cap = n_cap > d.max_cap ? n_cap : d.max_cap;
+    const int gx = (jb.W + B3GS_TILE - 1) / B3GS_TILE;
+    // (tile << idx_bits | index) fits 32 bits: ONE word per instance through emission, both passes and the blend kernels
+    // (which mask the index out) -- half the tile-sort traffic; the words live in val[].  Otherwise two words: the tile id
+    // in key[], the index in val[].
+    const int idx_bits = b3gs_packed_idx_bits(P, jb.W, jb.H);
+    const bool packed = idx_bits >= 0;
+    const int shift = packed ? idx_bits : 0;   // position of the tile id inside the sorted word
+    uint32_t* const key[2] = {packed ? jb.b.val[0] : jb.b.key[0], packed ? jb.b.val[1] : jb.b.key[1]};
+    uint32_t* const val[2] = {packed ? nullptr : jb.b.val[0], packed ? nullptr : jb.b.val[1]};
+
+    // ---- everything that depends on the round (comments: round 2 | round 1) ----
+    // tiles that take the Gaussians behind K1: still open after segment 1's blend | predicted open
+    const OpenMap open = open_map(r2 ? jb.im.open_rows : jb.im.pred_rows, jb.W, jb.H);
+    const uint32_t* open_count = r2 ? jb.im.header + 3 : nullptr;    // their number (0: no work) | not used
+    const uint32_t* n_ptr = r2 ? jb.g.header + 2 : jb.g.header;      // instances of the segment: N2 | N1
+    const uint32_t* off_ptr = r2 ? jb.g.header : nullptr;            // the segment starts at element N1 | 0
+    uint2* ranges = r2 ? jb.im.ranges2 : jb.im.ranges;               // (absolute positions in both)
+    // round 1 only: the scan's chunk offsets and tile totals, and the flagged lists -- those of a pair live with the view
+    // whose workgroups scanned both (round 2 keeps per-Gaussian offsets in soffs and needs none of them)
+    const int dn = r2 ? -1 : jb.order_from;
+    const GeomView& fg = (dn >= 0 && scan_partner_of(jobs, nviews, dn) == v) ? jobs[dn].g : jb.g;
+    const uint32_t *chunk_base = r2 ? nullptr : jb.g.scan_tmp, *tsum = r2 ? nullptr : jb.g.tsum;
+    const uint32_t *flist = r2 ? nullptr : fg.flist, *fcount = r2 ? nullptr : fg.fcount;
+
+    eb.j[v] = EmitJob{depth_order_of(jobs, v), jb.g.soffs, jb.g.srect, key[first], val[first], n_cap, gx, shift, jb.g.scount,
+                      open, open_count, off_ptr, chunk_base, flist, fcount, tsum};
+    tb.j[v] = SortJob{key[first], val[first], key[first ^ 1], val[first ^ 1], n_ptr, n_cap, b3gs_sort_blocks((int64_t)n_cap),
+                      shift, jb.b.hist, nullptr, off_ptr};
+    rb.j[v] = RangeJob{key[0], n_ptr, ranges, n_cap, shift, off_ptr};
+  }
+  return d;
+}
+
+// The stable split by tile id: pass p sorts byte p of the tile id (`bits` of it can be set), the last of the `passes` also
+// writes the ranges; step(p, bits) sees tb ready for pass p, then in and out are swapped (steps > passes: RepairArgs::tb whole)
+template <typename Step>
+static void build_tile_split(SortBatch& tb, const RangeBatch& rb, int passes, int tbits, int steps, Step step) {
+  for (int p = 0; p < steps; p++) {
+    if (p == passes - 1)
+      for (int v = 0; v < tb.n; v++) tb.j[v].ranges = rb.j[v].ranges;
+    step(p, min(8, max(0, tbits - 8 * p)));
+    swap_in_out(tb);
+  }
+}
+// ... as launches; a single-tile image has no pass, its ranges come from tile_ranges
+static void launch_tile_split(SortBatch& tb, const RangeBatch& rb, int passes, const TileListDims& d, hipStream_t s) {
+  build_tile_split(tb, rb, passes, d.tbits, passes, [&](int p, int bits) { radix_pass(tb, 8 * p, s, bits); });
+  if (passes == 0) hipLaunchKernelGGL(tile_ranges, dim3((d.max_cap + 255) / 256, tb.n), dim3(256), 0, s, rb);
+}
+
 void b3gs_launch_tile_lists_batch(int32_t P, int nviews, const BinJob* jobs, hipStream_t s) {
   if (nviews <= 0 || P <= 0) return;
   // views of different tile-sort depth cannot share the pass loop: run them one by one
@@ -1717,76 +1812,28 @@ void b3gs_launch_tile_lists_batch(int32_t P, int nviews, const BinJob* jobs, hip
     }
   }
 
-
   // ---- 3. emit (tile, index) instances in depth order into the buffer from which `passes` ping-pongs end in [0];
   //         every kernel clamps to min(N, capacity)
-  int tbits = 0;
-  for (int v = 0; v < nviews; v++) tbits = max(tbits, b3gs_tile_bits(jobs[v].W, jobs[v].H));
-  const int first = passes & 1;
   const int K1 = b3gs_seg1_count(jobs[0], P);
   EmitBatch eb;
   eb.n = nviews;
   eb.P = P;
   eb.K1 = K1;
   eb.first = 0;
-  {   // the chunking of b3gs_launch_depth_order_batch's scan
-    const int total_tiles = (P + SCAN_TILE - 1) / SCAN_TILE;
-    eb.tiles_per_chunk = (total_tiles + SCAN_MAX_CHUNKS - 1) / SCAN_MAX_CHUNKS;
-    eb.subs = eb.tiles_per_chunk * SCAN_ITEMS;
-  }
+  eb.tiles_per_chunk = scan_chunks(P).tiles_per_chunk;   // the chunking of b3gs_launch_depth_order_batch's scan
+  eb.subs = eb.tiles_per_chunk * SCAN_ITEMS;
   // segment 1 as 256-Gaussian sub-blocks, then one workgroup per 4096-Gaussian tile behind it (flagged lists)
   eb.dense_blocks = K1 < P ? K1 / 256 : (P + 255) / 256;
   eb.compact_blocks = K1 < P ? (P - K1 + SCAN_TILE - 1) / SCAN_TILE : 0;
   const int emit_blocks = eb.compact_blocks + eb.dense_blocks;
   SortBatch tb;
-  tb.n = nviews;
   RangeBatch rb;
-  rb.n = nviews;
-  uint32_t max_cap = 0;
-  for (int v = 0; v < nviews; v++) {
-    const BinJob& jb = jobs[v];
-    const uint32_t n_cap = (uint32_t)(jb.n_bound > 0 ? jb.n_bound : 0);
-    max_cap = n_cap > max_cap ? n_cap : max_cap;
-    const int gx = (jb.W + B3GS_TILE - 1) / B3GS_TILE;
-    const int idx_bits = b3gs_packed_idx_bits(P, jb.W, jb.H);
-    const OpenMap pm = open_map(jb.im.pred_rows, jb.W, jb.H);
-    // the flagged lists of a pair live with the view whose workgroups scanned both
-    const int dn = jb.order_from;
-    const GeomView& fg = (dn >= 0 && scan_partner_of(jobs, nviews, dn) == v) ? jobs[dn].g : jb.g;
-    if (idx_bits >= 0) {
-      // (tile << idx_bits | index) fits 32 bits: ONE word per instance through emission, both passes and the
-      // blend kernels (which mask the index out) -- half the tile-sort traffic.  The words ping-pong
-      // between val[first] and val[first ^ 1] and end in val[0], where the point list is expected.
-      eb.j[v] = EmitJob{depth_order_of(jobs, v), jb.g.soffs, jb.g.srect, jb.b.val[first], nullptr, n_cap, gx, idx_bits, jb.g.scount, pm, nullptr, nullptr, jb.g.scan_tmp,
-                        fg.flist, fg.fcount, jb.g.tsum};
-      tb.j[v] = SortJob{jb.b.val[first], nullptr, jb.b.val[first ^ 1], nullptr, jb.g.header, n_cap,
-                        b3gs_sort_blocks((int64_t)n_cap), idx_bits, jb.b.hist, nullptr, nullptr};
-      rb.j[v] = RangeJob{jb.b.val[0], jb.g.header, jb.im.ranges, n_cap, idx_bits, nullptr};
-    } else {
-      eb.j[v] = EmitJob{depth_order_of(jobs, v), jb.g.soffs, jb.g.srect, jb.b.key[first], jb.b.val[first], n_cap, gx, 0, jb.g.scount, pm, nullptr, nullptr, jb.g.scan_tmp,
-                        fg.flist, fg.fcount, jb.g.tsum};
-      tb.j[v] = SortJob{jb.b.key[first], jb.b.val[first], jb.b.key[first ^ 1], jb.b.val[first ^ 1], jb.g.header, n_cap,
-                        b3gs_sort_blocks((int64_t)n_cap), 0, jb.b.hist, nullptr, nullptr};
-      rb.j[v] = RangeJob{jb.b.key[0], jb.g.header, jb.im.ranges, n_cap, 0, nullptr};
-    }
-  }
-  if (max_cap == 0) return;  // im.ranges was reset to "empty" by the preprocess launch
+  const TileListDims d = build_tile_list_jobs(jobs, nviews, P, 1, eb, tb, rb);
+  if (d.max_cap == 0) return;  // im.ranges was reset to "empty" by the preprocess launch
   hipLaunchKernelGGL(emit_instances<false>, dim3(emit_blocks * nviews), dim3(256), 0, s, eb);
 
-  // ---- 4. stable split by tile id
-  for (int p = 0; p < passes; p++) {
-    if (p == passes - 1)
-      for (int v = 0; v < nviews; v++) tb.j[v].ranges = jobs[v].im.ranges;
-    radix_pass(tb, 8 * p, s, min(8, tbits - 8 * p));
-    for (int v = 0; v < nviews; v++) {
-      SortJob& j = tb.j[v];
-      const uint32_t* k = j.kin; const uint32_t* vv = j.vin;
-      j.kin = j.kout; j.vin = j.vout;
-      j.kout = const_cast<uint32_t*>(k); j.vout = const_cast<uint32_t*>(vv);  // stays null for packed keys
-    }
-  }
-  // ---- 5. per-tile [begin, end): produced by the last pass above; a single-tile image has no pass
-  if (passes == 0) hipLaunchKernelGGL(tile_ranges, dim3((max_cap + 255) / 256, nviews), dim3(256), 0, s, rb);
+  // ---- 4. stable split by tile id; 5. per-tile [begin, end): produced by its last pass
+  launch_tile_split(tb, rb, passes, d, s);
 }
 
 // The persistent repair launch needs ALL its workgroups resident at once (software grid barrier).  Its size is what the
@@ -1826,19 +1873,16 @@ void b3gs_launch_round2_batch(int32_t P, int nviews, const BinJob* jobs, hipStre
   for (int v = 0; v < nviews; v++)   // (the caller only enables K1 for batches of equal tile-sort depth)
     if (tile_sort_passes(jobs[v].W, jobs[v].H) != passes) return;
   const int rest = P - K1;
-  const int total_tiles = (rest + SCAN_TILE - 1) / SCAN_TILE;
+  const ScanChunks ch = scan_chunks(rest);
   Scan2Batch sc;
-  sc.n = nviews;
-  sc.P = P;
-  sc.K1 = K1;
-  sc.tiles_per_chunk = (total_tiles + SCAN_MAX_CHUNKS - 1) / SCAN_MAX_CHUNKS;
-  sc.nchunks = (total_tiles + sc.tiles_per_chunk - 1) / sc.tiles_per_chunk;
+  sc.n = nviews; sc.P = P; sc.K1 = K1;
+  sc.tiles_per_chunk = ch.tiles_per_chunk; sc.nchunks = ch.nchunks;
   for (int v = 0; v < nviews; v++) {
     const BinJob& jb = jobs[v];
-    sc.j[v] = Scan2Job{depth_order_of(jobs, v), jb.rect ? jb.rect : jb.g.rect, jb.rect ? jb.rect_stride : 1,
+    const RectRef rect = rect_of(jb);
+    sc.j[v] = Scan2Job{depth_order_of(jobs, v), rect.ptr, rect.stride,
                        jb.g.srect, jb.g.scount, jb.g.soffs, jb.g.scan_tmp, jb.g.header, jb.im.header, jb.n_out,
-                       open_map(jb.im.open_rows, jb.W, jb.H), jb.high_water, jb.overflow_flag,
-                       (uint32_t)(jb.n_bound > 0 ? (jb.n_bound < 0xFFFFFFFFll ? jb.n_bound : 0xFFFFFFFFll) : 0)};
+                       open_map(jb.im.open_rows, jb.W, jb.H), jb.high_water, jb.overflow_flag, bound32(jb)};
   }
   static const bool legacy = getenv("B3GS_ROUND2_LEGACY") != nullptr;
   bool one_launch = !legacy && passes >= 1 && passes <= 2 && jobs[0].im.header != nullptr;
@@ -1855,9 +1899,6 @@ void b3gs_launch_round2_batch(int32_t P, int nviews, const BinJob* jobs, hipStre
 
   // emission + stable split by tile id BEHIND segment 1 in the same ping-pong arrays (element offset N1 = header[0],
   // read on the device): the lists end in val[0] / key[0] like segment 1's, the ranges hold absolute positions
-  int tbits = 0;
-  for (int v = 0; v < nviews; v++) tbits = max(tbits, b3gs_tile_bits(jobs[v].W, jobs[v].H));
-  const int first = passes & 1;
   EmitBatch eb;
   eb.n = nviews;
   eb.P = P;
@@ -1868,32 +1909,9 @@ void b3gs_launch_round2_batch(int32_t P, int nviews, const BinJob* jobs, hipStre
   eb.compact_blocks = 0;
   eb.tiles_per_chunk = 1;
   SortBatch tb;
-  tb.n = nviews;
   RangeBatch rb;
-  rb.n = nviews;
-  uint32_t max_cap = 0;
-  for (int v = 0; v < nviews; v++) {
-    const BinJob& jb = jobs[v];
-    const uint32_t n_cap = (uint32_t)(jb.n_bound > 0 ? jb.n_bound : 0);
-    max_cap = n_cap > max_cap ? n_cap : max_cap;
-    const int gx = (jb.W + B3GS_TILE - 1) / B3GS_TILE;
-    const int idx_bits = b3gs_packed_idx_bits(P, jb.W, jb.H);
-    const OpenMap om = open_map(jb.im.open_rows, jb.W, jb.H);
-    if (idx_bits >= 0) {
-      eb.j[v] = EmitJob{depth_order_of(jobs, v), jb.g.soffs, jb.g.srect, jb.b.val[first], nullptr, n_cap, gx, idx_bits,
-                        jb.g.scount, om, jb.im.header + 3, jb.g.header, nullptr, nullptr, nullptr, nullptr};
-      tb.j[v] = SortJob{jb.b.val[first], nullptr, jb.b.val[first ^ 1], nullptr, jb.g.header + 2, n_cap,
-                        b3gs_sort_blocks((int64_t)n_cap), idx_bits, jb.b.hist, nullptr, jb.g.header};
-      rb.j[v] = RangeJob{jb.b.val[0], jb.g.header + 2, jb.im.ranges2, n_cap, idx_bits, jb.g.header};
-    } else {
-      eb.j[v] = EmitJob{depth_order_of(jobs, v), jb.g.soffs, jb.g.srect, jb.b.key[first], jb.b.val[first], n_cap, gx, 0,
-                        jb.g.scount, om, jb.im.header + 3, jb.g.header, nullptr, nullptr, nullptr, nullptr};
-      tb.j[v] = SortJob{jb.b.key[first], jb.b.val[first], jb.b.key[first ^ 1], jb.b.val[first ^ 1], jb.g.header + 2, n_cap,
-                        b3gs_sort_blocks((int64_t)n_cap), 0, jb.b.hist, nullptr, jb.g.header};
-      rb.j[v] = RangeJob{jb.b.key[0], jb.g.header + 2, jb.im.ranges2, n_cap, 0, jb.g.header};
-    }
-  }
-  if (max_cap == 0) return;
+  const TileListDims d = build_tile_list_jobs(jobs, nviews, P, 2, eb, tb, rb);
+  if (d.max_cap == 0) return;
   if (one_launch) {
     // the whole round as one persistent launch (repair_kernel): exits at once when no tile is open
     RepairArgs ra;
@@ -1907,18 +1925,7 @@ void b3gs_launch_round2_batch(int32_t P, int nviews, const BinJob* jobs, hipStre
       ra.max_blk = tb.j[v].nblk > ra.max_blk ? tb.j[v].nblk : ra.max_blk;
       any_val = any_val || tb.j[v].vout != nullptr;
     }
-    for (int p = 0; p < 2; p++) {
-      ra.bits[p] = min(8, max(0, tbits - 8 * p));
-      if (p == passes - 1)
-        for (int v = 0; v < nviews; v++) tb.j[v].ranges = jobs[v].im.ranges2;
-      ra.tb[p] = tb;
-      for (int v = 0; v < nviews; v++) {
-        SortJob& j = tb.j[v];
-        const uint32_t* k = j.kin; const uint32_t* vv = j.vin;
-        j.kin = j.kout; j.vin = j.vout;
-        j.kout = const_cast<uint32_t*>(k); j.vout = const_cast<uint32_t*>(vv);
-      }
-    }
+    build_tile_split(tb, rb, passes, d.tbits, 2, [&](int p, int bits) { ra.tb[p] = tb; ra.bits[p] = bits; });
     ra.barrier = jobs[0].im.header + B3GS_HDR_REPAIR_BARRIER;
     for (int v = 0; v < B3GS_MAX_FUSED_VIEWS; v++) ra.overflow[v] = v < nviews ? jobs[v].overflow_flag : nullptr;
     ra.spin_limit = repair_spin_limit();
@@ -1929,16 +1936,5 @@ void b3gs_launch_round2_batch(int32_t P, int nviews, const BinJob* jobs, hipStre
     return;
   }
   hipLaunchKernelGGL(emit_instances<true>, dim3((rest + 255) / 256, nviews), dim3(256), 0, s, eb);
-  for (int p = 0; p < passes; p++) {
-    if (p == passes - 1)
-      for (int v = 0; v < nviews; v++) tb.j[v].ranges = jobs[v].im.ranges2;
-    radix_pass(tb, 8 * p, s, min(8, tbits - 8 * p));
-    for (int v = 0; v < nviews; v++) {
-      SortJob& j = tb.j[v];
-      const uint32_t* k = j.kin; const uint32_t* vv = j.vin;
-      j.kin = j.kout; j.vin = j.vout;
-      j.kout = const_cast<uint32_t*>(k); j.vout = const_cast<uint32_t*>(vv);
-    }
-  }
-  if (passes == 0) hipLaunchKernelGGL(tile_ranges, dim3((max_cap + 255) / 256, nviews), dim3(256), 0, s, rb);
+  launch_tile_split(tb, rb, passes, d, s);
 }

@@ -793,6 +793,44 @@ def test_two_round_binning_edge_sizes(P, W, H):
                 assert torch.equal(x, y)
 
 
+def test_two_round_binning_with_two_word_instances():
+    """Two rounds when bits(P) + bits(tiles) > 32 (18 + 15 bits: 140k Gaussians, 128 x 129 tiles): the instances are
+    (tile, index) pairs, so the second round runs the value-carrying variant of its persistent launch on the key / value
+    flavour of the round-2 tables.  One view, no prediction to start from, tiles kept open: bit-identical to one round."""
+    import ctypes as C
+    from binocular3dgs_amd import _lib, synth
+    from binocular3dgs_amd.fused import FusedRasterizer
+    P, W, H = 140000, 2048, 2064
+    model = synth.synth_model(P, seed=11, device="cuda", width=W, height=H, requires_grad=False)
+    with torch.no_grad():
+        model._scaling += 1.0
+        model._opacity -= 2.0          # tiles stay open: the second round has work
+    cam = synth.synth_view_set(W, H, device="cuda")[0][0]
+    bg = torch.tensor([0.2, 0.1, 0.0], device="cuda")
+    views = [(cam, 0)]
+    res = []
+    for frac in (0.0, 0.1):
+        fr = FusedRasterizer(model, W, H, num_slots=1, seg1_fraction=frac)
+        fr.fit_capacity(views, bg)
+        fr.slots[0].img.zero_()        # (fit_capacity settles the prediction with a forward of its own: start from none)
+        with torch.no_grad():
+            out = fr.render_batch(views, bg)[0]
+        torch.cuda.synchronize()
+        assert not fr.overflowed() and int(fr.overflow_flag.item()) == 0
+        sl = fr.slots[0]
+        v = _lib.B3gsDebugViews()
+        _lib.check(_lib.lib().b3gs_debug_views(P, W, H, fr.capacity, sl.geom.data_ptr(), sl.binning.data_ptr(),
+                                               sl.img.data_ptr(), C.byref(v)), "b3gs_debug_views")
+        assert v.packed_idx_bits == -1 and v.tile_ids
+        if frac > 0.0:
+            missed, total = fr.repair_rate()
+            print(f"two-word two-round: N={fr.num_rendered()[0]} capacity={fr.capacity} missed={missed} of {total}")
+            assert missed >= 1, "the second round must have had work"
+        res.append([out[k].clone() for k in ("render", "rendered_depth", "rendered_alpha", "radii")])
+    for x, y in zip(res[1], res[0]):
+        assert torch.equal(x, y)
+
+
 def test_two_round_binning_overflow_is_detected():
     """Segment 2 sits behind segment 1 in the same arrays: N1 + N2 above the capacity truncates the lists (no write past
     the buffers) and shows up in the device-side N / high-water mark like a one-round overflow."""
