@@ -172,7 +172,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_mesh_components", "b3gs_mesh_clean_workspace_bytes", "b3gs_mesh_clean_count", "b3gs_mesh_clean_emit",
            "b3gs_mesh_sample_workspace_bytes", "b3gs_mesh_sample_count", "b3gs_mesh_sample_emit",
            "b3gs_nearest_workspace_bytes", "b3gs_nearest_grid", "b3gs_nearest_query",
-           "b3gs_cloud_score_workspace_bytes", "b3gs_cloud_score")
+           "b3gs_cloud_score_workspace_bytes", "b3gs_cloud_score",
+           # added to ABI 18: simplifying an extracted mesh
+           "b3gs_mesh_simplify_workspace_bytes", "b3gs_mesh_simplify_count", "b3gs_mesh_simplify_emit")
 
 _lib = None
 
@@ -336,6 +338,12 @@ def lib():
     L.b3gs_cloud_score_workspace_bytes.restype = C.c_size_t
     L.b3gs_cloud_score.argtypes = [I64, V, V, F, V, V, V]
     L.b3gs_cloud_score.restype = C.c_int
+    L.b3gs_mesh_simplify_workspace_bytes.argtypes = [I64, I64]
+    L.b3gs_mesh_simplify_workspace_bytes.restype = C.c_size_t
+    L.b3gs_mesh_simplify_count.argtypes = [I32, I64, V, V, F, V, V]
+    L.b3gs_mesh_simplify_count.restype = C.c_int
+    L.b3gs_mesh_simplify_emit.argtypes = [I32, I64, V, V, V, F, I32, V, I64, I64, V, V, V, V]
+    L.b3gs_mesh_simplify_emit.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

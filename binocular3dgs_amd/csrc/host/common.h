@@ -77,5 +77,6 @@ void bind_sweep(pybind11::module_& m);
 void bind_jpeg(pybind11::module_& m);
 void bind_mesh(pybind11::module_& m);
 void bind_meshtools(pybind11::module_& m);
+void bind_simplify(pybind11::module_& m);
 
 }  // namespace b3

@@ -55,4 +55,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_jpeg(m);
   b3::bind_mesh(m);
   b3::bind_meshtools(m);
+  b3::bind_simplify(m);
 }

@@ -2,12 +2,16 @@
                                             [--resolution 256 | --voxel_size S] [--truncation_voxels 4] [--alpha_min 0.5]
                                             [--min_weight 1] [--bounds x0 y0 z0 x1 y1 z1]
                                             [--keep_largest 0] [--min_triangles 0]
+                                            [--simplify K | --target_triangles N] [--placement quadric|mean]
 
 A triangle mesh of a trained model: the point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply is rendered from
 the chosen cameras, depth, alpha and colour are fused into a TSDF volume and the zero level set is extracted, all on the
 device (mesh.fuse_model).  Writes <model_path>/mesh/iteration_<it>/mesh.ply (binary PLY, coloured vertices) and prints the
 voxel, vertex and triangle counts.  --keep_largest K keeps the K components with the most triangles (ties at the K-th
 all survive), --min_triangles M the components with at least M (mesh_tools.clean); with both at 0 the step is not run.
+--simplify K clusters the vertices on a grid of K voxels (mesh_tools.simplify), --target_triangles N searches the smallest
+such grid that leaves at most N triangles (mesh_tools.simplify_to); either runs after the cleaning step and prints the counts
+before and after.  --placement says where a cluster's vertex goes: the minimiser of its faces' quadric, or the members' mean.
 
 The model and the cameras are found the way spiral.py finds them: source path, images folder, image resolution, background,
 SH degree, dataset name and view count come from <model_path>/cfg_args; the command line wins.  A model folder whose dataset
@@ -41,7 +45,27 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
     p.add_argument("--keep_largest", type=int, default=0, help="keep the K largest connected components (0: all)")
     p.add_argument("--min_triangles", type=int, default=0, help="drop the components with fewer triangles (0: none)")
+    simp = p.add_mutually_exclusive_group()
+    simp.add_argument("--simplify", type=_positive_float, default=None, metavar="K",
+                      help="cluster the vertices on a grid whose cell is K voxels (K > 0)")
+    simp.add_argument("--target_triangles", type=_positive_int, default=None, metavar="N",
+                      help="search the smallest cell that leaves at most N triangles")
+    p.add_argument("--placement", choices=("quadric", "mean"), default="quadric", help="where a cluster's vertex goes")
     return p
+
+
+def _positive_float(text: str) -> float:
+    v = float(text)
+    if not (v > 0.0 and v < float("inf")):
+        raise argparse.ArgumentTypeError("a positive, finite number is needed")
+    return v
+
+
+def _positive_int(text: str) -> int:
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("at least 1")
+    return v
 
 
 def cameras_from_json(path: str, device="cuda"):
@@ -78,7 +102,7 @@ def load_cameras(model_path: str, cfg: dict, source_path, views: str, device="cu
 
 def run(model_path: str, source_path=None, iteration: int = -1, views: str = "train", resolution=None, voxel_size=None,
         truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, bounds=None,
-        keep_largest: int = 0, min_triangles: int = 0) -> str:
+        keep_largest: int = 0, min_triangles: int = 0, simplify=None, target_triangles=None, placement: str = "quadric") -> str:
     from . import mesh
     from .gaussian_model import GaussianModel
     from .spiral import max_iteration, read_cfg_args
@@ -100,6 +124,16 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
         vertices, colours, faces, st = mesh_tools.clean(vertices, colours, faces, keep_largest, min_triangles, return_stats=True)
         print(f"{st['components']} components, {st['kept']} kept: dropped {st['vertices_dropped']} vertices, "
               f"{st['triangles_dropped']} triangles")
+    if simplify is not None or target_triangles is not None:
+        from . import mesh_tools
+        before = (vertices.shape[0], faces.shape[0])
+        if simplify is not None:
+            cell = float(simplify) * vol.voxel_size
+            vertices, colours, faces = mesh_tools.simplify(vertices, colours, faces, cell, placement)
+        else:
+            vertices, colours, faces, cell = mesh_tools.simplify_to(vertices, colours, faces, target_triangles, placement)
+        print(f"simplified ({placement}, cell {cell:g} = {cell / vol.voxel_size:g} voxels): {before[0]} vertices, {before[1]} triangles "
+              f"-> {vertices.shape[0]} vertices, {faces.shape[0]} triangles")
     out_dir = os.path.join(model_path, "mesh", "iteration_{}".format(it))
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "mesh.ply")
@@ -114,7 +148,7 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
 def main(argv=None) -> int:
     a = parser().parse_args(argv)
     run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
-        a.min_weight, a.bounds, a.keep_largest, a.min_triangles)
+        a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement)
     return 0
 
 

@@ -1,4 +1,5 @@
-"""Cleaning and scoring an extracted mesh, on the device (csrc/meshtools.hip, ABI 18).
+"""Cleaning, scoring and simplifying an extracted mesh, on the device (csrc/meshtools.hip, ABI 18, INTEGRATION.md section 13;
+csrc/simplify.hip).
 
     labels, tri_count = components(vertices, faces)                      # int32 [V] each; no host read
     vertices, colours, faces = clean(vertices, colours, faces, keep_largest=1)
@@ -6,8 +7,10 @@
     d = nearest_distances(a, b, max_dist)                                # float32 [Na]: the float32 brute force, bit for bit
     score = score_clouds(recon, gt, max_dist, tau)                       # accuracy, completeness, chamfer, precision, recall, fscore
     score = score_mesh(vertices, faces, gt, spacing, max_dist, tau)
+    vertices, colours, faces = simplify(vertices, colours, faces, cell, placement="quadric")     # vertex clustering
+    vertices, colours, faces, cell = simplify_to(vertices, colours, faces, target_triangles)
 
-The arithmetic is stated in include/b3gs_raster.h and restated in numpy by tests/meshtools_ref.py.  Policy that is not hot
+The arithmetic is stated in include/b3gs_raster.h and restated in numpy by tests/meshtools_ref.py and tests/simplify_ref.py.  Policy that is not hot
 lives here in torch: the component threshold of `clean` (a topk of the triangle counts, kept on the device).
 
 The score is the point-to-point measure of the DTU surface benchmark (distances both ways between points on the
@@ -156,3 +159,106 @@ def score_mesh(vertices: torch.Tensor, faces: torch.Tensor, gt: torch.Tensor, sp
                mask_gt: Optional[torch.Tensor] = None, return_distances: bool = False) -> dict:
     """sample_surface(vertices, faces, spacing), then score_clouds against gt."""
     return score_clouds(sample_surface(vertices, faces, spacing), gt, max_dist, tau, None, mask_gt, return_distances)
+
+
+# ---- simplification: vertex clustering with quadric-optimal representatives (csrc/simplify.hip) -------------------------------
+PLACEMENTS = {"quadric": 0, "mean": 1}     # B3GS_SIMPLIFY_QUADRIC / _MEAN
+MAX_CELLS = 1024                           # cells per axis of the clustering grid
+MAX_TRIALS = 12                            # count-only trials of simplify_to
+
+
+def smallest_cell(extent: float) -> float:
+    """The smallest float32 `cell` with floor(extent / cell) <= 1023 in float32, i.e. at most 1024 cells along an edge of
+    length `extent` that starts at the grid's origin."""
+    import numpy as np
+    e = np.float32(extent)
+    c = np.float32(e / np.float32(MAX_CELLS))
+    while c > 0 and np.floor(e / np.nextafter(c, np.float32(0))) < MAX_CELLS:
+        c = np.nextafter(c, np.float32(0))
+    while not (c > 0 and np.floor(e / c) < MAX_CELLS):
+        c = np.nextafter(c, np.float32(np.inf))
+    return float(c)
+
+
+def _extent_of(word: int) -> float:
+    import struct
+    return struct.unpack("<f", struct.pack("<I", int(word) & 0xFFFFFFFF))[0]
+
+
+def _simplify_count(vertices, faces, cell, what):
+    """count, the ONE host read, and the errors that ride on it -> (workspace, the nine totals)"""
+    from . import _C
+    ws, totals = _C.mesh_simplify_count(vertices, _faces(faces), float(cell))
+    t = totals.tolist()                                                   # the one host read
+    bad, nonfinite, over = t[2], t[3], t[4]
+    if bad:
+        raise ValueError(f"{what}: {bad} triangles name a vertex outside 0 .. {vertices.shape[0] - 1}")
+    if nonfinite:
+        raise ValueError(f"{what}: {nonfinite} vertices have a coordinate that is not finite")
+    if over:
+        raise ValueError(f"{what}: {over} vertices lie beyond {MAX_CELLS} cells of {float(cell):g} along an axis: "
+                         f"the smallest admissible cell is {smallest_cell(_extent_of(t[8]))!r}")
+    return ws, t
+
+
+def simplify(vertices: torch.Tensor, colours: torch.Tensor, faces: torch.Tensor, cell: float, placement: str = "quadric",
+             return_stats: bool = False):
+    """Vertex clustering on a grid of edge `cell` (world units) whose origin is the lower corner of the vertices' box: every
+    cluster that a surviving triangle names becomes one vertex, at the minimiser of its faces' quadric ("quadric": pulled to
+    the planes of the faces that touch the cluster, never further than `cell` from the mean) or at the mean of its members
+    ("mean"); a triangle with two corners in one cluster is dropped, and of the triangles that name the same three clusters
+    the first stays -> (vertices, colours, faces), triangles in input order with their winding.  Errors, not clamps: more
+    than 1024 cells along an axis, a coordinate that is not finite, a face index outside 0 .. V-1.  One host read: the totals
+    (and the error counts and statistics), between count and emit."""
+    from . import _C
+    if placement not in PLACEMENTS:
+        raise ValueError(f"simplify: placement is one of {sorted(PLACEMENTS)}")
+    if not cell > 0.0:
+        raise ValueError("simplify: the cell is positive")
+    ws, t = _simplify_count(vertices, faces, cell, "simplify")
+    out = _C.mesh_simplify_emit(vertices, colours, faces, float(cell), PLACEMENTS[placement], ws, t[0], t[1])
+    if return_stats:
+        return out + ({"clusters": t[5], "vertices_dropped": vertices.shape[0] - t[0], "triangles_degenerate": t[6],
+                       "triangles_duplicate": t[7]},)
+    return out
+
+
+def bisect_cell(count_triangles, extent: float, target_triangles: int, trials: int = MAX_TRIALS):
+    """The search of simplify_to as host logic over `count_triangles(cell) -> int`: geometric bisection of the cell between
+    the smallest admissible one (extent / 1024) and `extent`, at most `trials` calls -> (the smallest tried cell whose count
+    is at most the target, its count).  ValueError when even `extent` leaves more than the target."""
+    lo = smallest_cell(extent)
+    n = count_triangles(lo)
+    if n <= target_triangles:
+        return lo, n
+    hi = float(extent)
+    best = count_triangles(hi)
+    if best > target_triangles:
+        raise ValueError(f"simplify_to: a cell of the whole extent ({hi:g}) still leaves {best} triangles")
+    for _ in range(trials - 2):
+        mid = (lo * hi) ** 0.5
+        if not lo < mid < hi:
+            break
+        n = count_triangles(mid)
+        if n <= target_triangles:
+            hi, best = mid, n
+        else:
+            lo = mid
+    return hi, best
+
+
+def simplify_to(vertices: torch.Tensor, colours: torch.Tensor, faces: torch.Tensor, target_triangles: int, placement: str = "quadric"):
+    """simplify() at the smallest cell, of at most 12 tried by geometric bisection between extent / 1024 and extent (the
+    longest edge of the vertices' box), that leaves at most `target_triangles` triangles -> (vertices, colours, faces, cell).
+    Host reads: the extent, one per count-only trial, and the one of the final simplify()."""
+    if target_triangles < 1:
+        raise ValueError("simplify_to: target_triangles is at least 1")
+    if placement not in PLACEMENTS:
+        raise ValueError(f"simplify_to: placement is one of {sorted(PLACEMENTS)}")
+    if vertices.shape[0] == 0 or faces.shape[0] == 0:
+        raise ValueError("simplify_to: the mesh is empty")
+    extent = float((vertices.amax(dim=0) - vertices.amin(dim=0)).max())
+    if not (extent > 0.0 and extent < float("inf")):
+        raise ValueError("simplify_to: the vertices span no finite, positive extent")
+    cell, _ = bisect_cell(lambda c: _simplify_count(vertices, faces, c, "simplify_to")[1][1], extent, int(target_triangles))
+    return simplify(vertices, colours, faces, cell, placement) + (cell,)

@@ -786,6 +786,61 @@ size_t b3gs_cloud_score_workspace_bytes(int64_t N);
 int b3gs_cloud_score(int64_t N, const float* dist, const uint8_t* mask, float tau, double* out, void* workspace,
                      b3gs_stream_t stream);
 
+/* ---- simplifying an extracted mesh: quadric vertex clustering (ABI 18, added entry points; binocular3dgs_amd/mesh_tools.py, INTEGRATION.md
+ * section 14) ------------------------------------------------------------------------------------------------------------------
+ * Three entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays (a binding of
+ * ABI 18 keeps working against this library, and tests/test_meshtools_cpu.py pins it).
+ * A Rossignac-Borrel grid with Lindstrom's quadric-optimal representatives.  Integer work, stable sorts, ordered scans, single
+ * correctly rounded float32 operations, and fp64 statements that ONE thread per cluster executes in one fixed order:
+ * tests/simplify_ref.py restates every statement in numpy and every output agrees bit for bit.  Nothing synchronises or reads
+ * the device; the workspace is 256-byte aligned, b3gs_mesh_simplify_workspace_bytes(V, F) bytes (0 for bad sizes; about
+ * 80 bytes per triangle and 50 per vertex).  V <= 2^31 - 1, 3 F <= 2^31 - 1, cell > 0 and finite.
+ *
+ * 1. grid      o = the per-axis float32 minimum of the V vertices (computed on the device)
+ *              c_a = floor((x_a - o_a) / cell)            two rounded float32 operations, then the floor, per axis
+ *              key = (c_z << 20) | (c_y << 10) | c_x       a c_a outside 0 .. 1023 (or NaN) is counted as an error, not clamped
+ * 2. clusters  the vertices are sorted stably by key; the cluster id of a vertex is the rank of its key among the distinct
+ *              keys, ascending; the members of a cluster are in vertex-index order
+ * 3. faces     (a, b, c) = the cluster ids of the corners; two equal ids: the face is degenerate and dropped.  Among the
+ *              faces with the same unordered {a, b, c} the one with the smallest face index survives, whatever the winding of
+ *              the others (a stable sort by max, then by mid, then by min, the three orders composed, and a boundary pass).
+ *              Survivors come out in input face order with the input's corner order.
+ * 4. vertices  a cluster survives when a surviving face names it; new ids are the ranks among the survivors, in cluster
+ *              order.  A mesh that collapses completely gives nverts = ntris = 0 and no error.
+ * 5. colour    per channel (2 sum + n) / (2 n) in integers over the n members
+ * 6. mean      m = (the fp64 sum of the member positions, in member order) / n, per axis;  position = float32(m)
+ * 7. quadric   ONE THREAD PER CLUSTER k walks, in face-index order, the input faces with at least one corner in k (a face
+ *              once, even with two or three corners in k; the faces step 3 drops included): the (cluster, face) incidence
+ *              list is built on the device and sorted stably by cluster.  In fp64 from the float32 coordinates, m kept in fp64,
+ *              one operation per statement:
+ *                u = p1 - p0, v = p2 - p0;  n = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x);  q = p0 - m
+ *                d = (n_x q_x + n_y q_y) + n_z q_z
+ *                A00 += n_x n_x, A01 += n_x n_y, A02 += n_x n_z, A11 += n_y n_y, A12 += n_y n_z, A22 += n_z n_z
+ *                r0 += d n_x, r1 += d n_y, r2 += d n_z
+ *              lambda = 1e-3 ((A00 + A11) + A22);  lambda == 0: y = 0.  Otherwise (A + lambda I) y = r by Cholesky:
+ *                a00 = A00 + lambda, a11 = A11 + lambda, a22 = A22 + lambda
+ *                l00 = sqrt(a00), l10 = A01 / l00, l20 = A02 / l00
+ *                l11 = sqrt(a11 - l10 l10), l21 = (A12 - l20 l10) / l11, l22 = sqrt((a22 - l20 l20) - l21 l21)
+ *                z0 = r0 / l00, z1 = (r1 - l10 z0) / l11, z2 = ((r2 - l20 z0) - l21 z1) / l22
+ *                y2 = z2 / l22, y1 = (z1 - l21 y2) / l11, y0 = ((z0 - l10 y1) - l20 y2) / l00
+ *              max |y_a| > cell, or a y_a that is not finite: y = 0.  position = float32(m + y), per axis.
+ * 8. the translation unit is compiled with -ffp-contract=off; no floating-point atomic anywhere.
+ *
+ * count leaves nine int64 at the START of the workspace: {vertices out, triangles out, triangles with an index outside
+ * 0 .. V-1, vertices with a coordinate that is not finite, vertices outside the 1024 cells of an axis, clusters, degenerate
+ * triangles, duplicate triangles, the float32 bits of the largest box edge}.  A caller reads them once, treats words 2 .. 4 as
+ * errors, and calls emit(nverts, ntris) with the arguments of count and the same workspace; emit fills out_vertices
+ * [nverts, 3], out_colours [nverts, 3], out_faces [ntris, 3], writes nothing past those counts (which are at most V and F,
+ * so they fit int32) and may be called again, e.g. once per placement. */
+#define B3GS_SIMPLIFY_QUADRIC 0
+#define B3GS_SIMPLIFY_MEAN 1
+size_t b3gs_mesh_simplify_workspace_bytes(int64_t V, int64_t F);
+int b3gs_mesh_simplify_count(int32_t V, int64_t F, const float* vertices, const int32_t* faces, float cell, void* workspace,
+                             b3gs_stream_t stream);
+int b3gs_mesh_simplify_emit(int32_t V, int64_t F, const float* vertices, const uint8_t* colours, const int32_t* faces, float cell,
+                            int32_t placement, void* workspace, int64_t nverts, int64_t ntris, float* out_vertices,
+                            uint8_t* out_colours, int32_t* out_faces, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
