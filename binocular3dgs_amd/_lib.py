@@ -174,7 +174,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_nearest_workspace_bytes", "b3gs_nearest_grid", "b3gs_nearest_query",
            "b3gs_cloud_score_workspace_bytes", "b3gs_cloud_score",
            # added to ABI 18: simplifying an extracted mesh
-           "b3gs_mesh_simplify_workspace_bytes", "b3gs_mesh_simplify_count", "b3gs_mesh_simplify_emit")
+           "b3gs_mesh_simplify_workspace_bytes", "b3gs_mesh_simplify_count", "b3gs_mesh_simplify_emit",
+           # added to ABI 18: rendering an extracted mesh
+           "b3gs_mesh_raster_workspace_bytes", "b3gs_mesh_raster_batch", "b3gs_mesh_resolve_batch")
 
 _lib = None
 
@@ -344,6 +346,12 @@ def lib():
     L.b3gs_mesh_simplify_count.restype = C.c_int
     L.b3gs_mesh_simplify_emit.argtypes = [I32, I64, V, V, V, F, I32, V, I64, I64, V, V, V, V]
     L.b3gs_mesh_simplify_emit.restype = C.c_int
+    L.b3gs_mesh_raster_workspace_bytes.argtypes = [I32, I64, I64, I32, I32]
+    L.b3gs_mesh_raster_workspace_bytes.restype = C.c_size_t
+    L.b3gs_mesh_raster_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, I32, I32, I32, V, V, V]
+    L.b3gs_mesh_raster_batch.restype = C.c_int
+    L.b3gs_mesh_resolve_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, V, V, V, I32, V, V, V, V, V, V]
+    L.b3gs_mesh_resolve_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,7 +1,7 @@
 """python -m binocular3dgs_amd.extract_mesh -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--views train|test|all]
                                             [--resolution 256 | --voxel_size S] [--truncation_voxels 4] [--alpha_min 0.5]
                                             [--min_weight 1] [--bounds x0 y0 z0 x1 y1 z1]
-                                            [--keep_largest 0] [--min_triangles 0]
+                                            [--keep_largest 0] [--min_triangles 0] [--cull_unseen [--min_pixels 1]]
                                             [--simplify K | --target_triangles N] [--placement quadric|mean]
 
 A triangle mesh of a trained model: the point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply is rendered from
@@ -9,6 +9,9 @@ the chosen cameras, depth, alpha and colour are fused into a TSDF volume and the
 device (mesh.fuse_model).  Writes <model_path>/mesh/iteration_<it>/mesh.ply (binary PLY, coloured vertices) and prints the
 voxel, vertex and triangle counts.  --keep_largest K keeps the K components with the most triangles (ties at the K-th
 all survive), --min_triangles M the components with at least M (mesh_tools.clean); with both at 0 the step is not run.
+--cull_unseen renders the mesh into the cameras of --views (mesh_render.cull_unseen) and drops the triangles that win fewer
+than --min_pixels pixels over all of them, e.g. blobs inside or behind the observed surface; it runs after the cleaning step
+and before the simplification.
 --simplify K clusters the vertices on a grid of K voxels (mesh_tools.simplify), --target_triangles N searches the smallest
 such grid that leaves at most N triangles (mesh_tools.simplify_to); either runs after the cleaning step and prints the counts
 before and after.  --placement says where a cluster's vertex goes: the minimiser of its faces' quadric, or the members' mean.
@@ -51,6 +54,8 @@ def parser() -> argparse.ArgumentParser:
     simp.add_argument("--target_triangles", type=_positive_int, default=None, metavar="N",
                       help="search the smallest cell that leaves at most N triangles")
     p.add_argument("--placement", choices=("quadric", "mean"), default="quadric", help="where a cluster's vertex goes")
+    p.add_argument("--cull_unseen", action="store_true", help="drop the triangles no camera of --views sees")
+    p.add_argument("--min_pixels", type=_positive_int, default=1, help="with --cull_unseen: pixels a triangle must win to stay")
     return p
 
 
@@ -102,7 +107,8 @@ def load_cameras(model_path: str, cfg: dict, source_path, views: str, device="cu
 
 def run(model_path: str, source_path=None, iteration: int = -1, views: str = "train", resolution=None, voxel_size=None,
         truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, bounds=None,
-        keep_largest: int = 0, min_triangles: int = 0, simplify=None, target_triangles=None, placement: str = "quadric") -> str:
+        keep_largest: int = 0, min_triangles: int = 0, simplify=None, target_triangles=None, placement: str = "quadric",
+        cull_unseen: bool = False, min_pixels: int = 1) -> str:
     from . import mesh
     from .gaussian_model import GaussianModel
     from .spiral import max_iteration, read_cfg_args
@@ -124,6 +130,11 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
         vertices, colours, faces, st = mesh_tools.clean(vertices, colours, faces, keep_largest, min_triangles, return_stats=True)
         print(f"{st['components']} components, {st['kept']} kept: dropped {st['vertices_dropped']} vertices, "
               f"{st['triangles_dropped']} triangles")
+    if cull_unseen:
+        from . import mesh_render
+        before = (vertices.shape[0], faces.shape[0])
+        vertices, colours, faces = mesh_render.cull_unseen(vertices, colours, faces, cams, min_pixels)
+        print(f"culled: {before[1] - faces.shape[0]} of {before[1]} triangles seen by no camera, {before[0] - vertices.shape[0]} vertices")
     if simplify is not None or target_triangles is not None:
         from . import mesh_tools
         before = (vertices.shape[0], faces.shape[0])
@@ -148,7 +159,7 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
 def main(argv=None) -> int:
     a = parser().parse_args(argv)
     run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
-        a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement)
+        a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement, a.cull_unseen, a.min_pixels)
     return 0
 
 

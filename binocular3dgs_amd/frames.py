@@ -414,7 +414,7 @@ VIDEO_NAMES = ("out_{}.avi", "out_depth_{}.avi", "out_cdepth_{}.avi")     # the 
 
 # ---- drivers -----------------------------------------------------------------------------------------------------------
 def render_path(model, cameras: Sequence, bg: torch.Tensor, out_dir: Optional[str] = None, *, batch: int = MAX_BATCH,
-                percentile: float = 99., video=None, png: bool = True, fps: float = 25.0, quality: int = 90):
+                percentile: float = 99., video=None, png: bool = True, fps: float = 25.0, quality: int = 90, source=None):
     """spiral.py's render_set: every camera rendered (up to `batch` <= 8 views of one W x H per launch, evaluation's renderer)
     and encoded on the device.
     out_dir None: -> per camera {"rgb", "depth", "cdepth"} uint8 [H,W,3] device tensors.
@@ -424,8 +424,13 @@ def render_path(model, cameras: Sequence, bg: torch.Tensor, out_dir: Optional[st
                   straight from the device tensors, and <directory>/out_<stem>.avi, out_depth_<stem>.avi, out_cdepth_<stem>.avi
                   (Motion-JPEG, `fps`, `quality`) are written at the end; every camera must have the same size.
                   -> {"png": the PNG paths (empty without out_dir or with png=False), "video": the three AVI paths}.
-                  png=False skips the PNG files and the raw host copy they need."""
+                  png=False skips the PNG files and the raw host copy they need.
+    source:       where the images come from: an iterable of (camera indices, per-view {"render", "rendered_depth",
+                  "rendered_alpha"} on the device) per batch of at most 8 views of one size; default: the model through
+                  evaluation's renderer (`model` is not used otherwise; mesh_render.batches is another source)."""
     from . import evaluate
+    if source is None:
+        source = evaluate._batches(model, cameras, bg, batch, full=True)
     want_png = out_dir is not None and png
     if video is not None:
         vdir, stem = os.path.split(video) if isinstance(video, str) else (video[0], video[1])
@@ -442,7 +447,7 @@ def render_path(model, cameras: Sequence, bg: torch.Tensor, out_dir: Optional[st
         os.makedirs(out_dir, exist_ok=True)
     try:
         with torch.no_grad():
-            for idx, outs in evaluate._batches(model, cameras, bg, batch, full=True):
+            for idx, outs in source:
                 enc = encode_frames([o["render"] for o in outs], [o["rendered_depth"] for o in outs],
                                     [o["rendered_alpha"] for o in outs], percentile=percentile)
                 if video is not None:

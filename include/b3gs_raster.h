@@ -841,6 +841,69 @@ int b3gs_mesh_simplify_emit(int32_t V, int64_t F, const float* vertices, const u
                             int32_t placement, void* workspace, int64_t nverts, int64_t ntris, float* out_vertices,
                             uint8_t* out_colours, int32_t* out_faces, b3gs_stream_t stream);
 
+/* ---- rendering an extracted mesh: a triangle rasterizer (ABI 18, added entry points; binocular3dgs_amd/mesh_render.py, INTEGRATION.md
+ * section 15) ------------------------------------------------------------------------------------------------------------------
+ * Three entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * Up to B3GS_MAX_MESH_VIEWS views of one W x H of one mesh (vertices float32 [V, 3], colours uint8 [V, 3], faces int32 [F, 3]):
+ * per pixel the nearest triangle and its depth.  Membership is 64-bit integer work, every float statement is one correctly
+ * rounded operation (the translation unit is compiled with -ffp-contract=off), the visibility buffer is a minimum over a set:
+ * tests/meshraster_ref.py restates every statement in numpy and every output agrees bit for bit, whatever the launch geometry
+ * and whichever path took a triangle.  Nothing synchronises or reads the device; both calls are capturable in a graph.
+ * cameras: HOST float32 [nviews, 14] rows of (world -> camera rotation, 9 row-major; translation, 3; fx, fy in pixels), read
+ * during the call.  1 <= nviews <= 8, 1 <= W, H <= B3GS_MAX_MESH_IMAGE, V and F <= 2^31 - 1.
+ *
+ * 1. vertex    p_r = ((rot[3r] x + rot[3r+1] y) + rot[3r+2] z) + trans[r], r = 0, 1, 2          camera space, float32
+ *              sx = fx * (p_0 / p_2) + (0.5 W - 0.5),  sy = fy * (p_1 / p_2) + (0.5 H - 0.5)      pixel centres at integers
+ *              X = (int) rint(sx * 256), Y likewise (half to even): 8 sub-pixel bits
+ * 2. rejected  a vertex is good when p_2 > 0.2 (the renderer's near plane), p_2 is finite and |rint(sx * 256)|,
+ *              |rint(sy * 256)| < 2^22 (a NaN anywhere fails one of these).  A triangle with a vertex that is not good, or
+ *              with an index outside 0 .. V-1, is rejected: not clipped, not drawn, counted.  counts (device int32 [9], zeroed
+ *              by the call): [v] = triangles rejected in view v, [8] = triangles with an index outside 0 .. V-1 (once, not per
+ *              view; they are part of every [v] too).
+ * 3. coverage  A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0), the doubled area (int64); A = 0 covers nothing; A > 0 is
+ *              clockwise as seen (y points down): the normal (p1 - p0) x (p2 - p0) points away, and cull_backface drops it.
+ *              With s = sign(A): for k = 0, 1, 2, p = k + 1, q = k + 2 (mod 3), (dx, dy) = s (X_q - X_p, Y_q - Y_p),
+ *                E_k(i, j) = dx (256 j - Y_p) - dy (256 i - X_p)                                   int64, below 2^48
+ *              Pixel (i, j) is covered when, for every k, E_k > 0, or E_k = 0 and the edge is a top or a left one:
+ *              dy < 0, or dy = 0 and dx > 0.  Two triangles that share an edge walk it in opposite directions, so a pixel
+ *              centre on it belongs to exactly one of them.  Both windings cover.
+ * 4. depth     b_k = (float)((double)E_k / (double)(s A)),  w_k = b_k * (1 / p_2 of vertex k),
+ *              iz = (w_0 + w_1) + w_2,  z = 1 / iz: the perspective-correct camera-space z (the `d` of section 12)
+ * 5. buffer    one uint64 per pixel and view, all ones = empty; a covered pixel takes the minimum of
+ *              (float bits of z << 32) | triangle index: the nearest z, among equal z the smallest index.  Integer atomics.
+ * 6. paths     the clamped box of a triangle is i = max(ceil(min X / 256), 0) .. min(floor(max X / 256), W - 1), j likewise;
+ *              box = its pixel count.  box <= small_box: the lane that set the triangle up walks it; box <= wave_box: one
+ *              wave, in 8 x 8 pixel blocks from the box's corner, a block skipped when some E_k is below its bound at the block
+ *              corner where it is largest; beyond: one workgroup of 16 waves.  The two lists are compacted in triangle order by
+ *              the ordered scan.  small_box, wave_box < 0: the defaults B3GS_MESH_SMALL_BOX, B3GS_MESH_WAVE_BOX; any values
+ *              give the same output (0, 2^31 - 1: everything through one wave each; 0, 0: one workgroup each).
+ * 7. resolve   a second call with the same cameras, mesh and workspace; thread = pixel.  The winner's E_k, b_k, w_k and z
+ *              again from the same integers.  triangle_id int32 [n, H, W] (-1: empty), depth float32 [n, 1, H, W] = z (0),
+ *              alpha float32 [n, 1, H, W] = 1 (0), colour float32 [n, 3, H, W] (bg, device float32 [3]; NULL: 0):
+ *                B3GS_MESH_SHADE_COLOUR  (((w_0 c_0 + w_1 c_1) + w_2 c_2) * z) / 255 per channel, c the uint8 vertex colours
+ *                B3GS_MESH_SHADE_NORMAL  u = p1 - p0, v = p2 - p0 (camera space, statement 1 again),
+ *                                        n = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x),
+ *                                        l = sqrt((n_x n_x + n_y n_y) + n_z n_z) (correctly rounded), n / l per component (0
+ *                                        when l is 0 or not finite), negated when A > 0, then (n + 1) * 0.5
+ *              face_pixels int32 [F]: + 1 per pixel the triangle wins (an integer atomic; it accumulates until the caller
+ *              zeroes it).  Every output pointer may be NULL.
+ * workspace: b3gs_mesh_raster_workspace_bytes(nviews, V, F, W, H) bytes (0: bad sizes; 16 bytes per view and vertex, 8 per view
+ * and pixel, 9 per view and triangle), 256-byte aligned, no initial content needed. */
+#define B3GS_MAX_MESH_VIEWS 8
+#define B3GS_MAX_MESH_IMAGE 16384
+#define B3GS_MESH_SMALL_BOX 32
+#define B3GS_MESH_WAVE_BOX 4096
+#define B3GS_MESH_SHADE_COLOUR 0
+#define B3GS_MESH_SHADE_NORMAL 1
+size_t b3gs_mesh_raster_workspace_bytes(int32_t nviews, int64_t V, int64_t F, int32_t W, int32_t H);
+int b3gs_mesh_raster_batch(int32_t nviews, const float* cameras, int32_t W, int32_t H, int32_t V, int64_t F, const float* vertices,
+                           const int32_t* faces, int32_t cull_backface, int32_t small_box, int32_t wave_box, void* workspace,
+                           int32_t* counts, b3gs_stream_t stream);
+int b3gs_mesh_resolve_batch(int32_t nviews, const float* cameras, int32_t W, int32_t H, int32_t V, int64_t F, const float* vertices,
+                            const uint8_t* colours, const int32_t* faces, const void* workspace, const float* bg, int32_t shading,
+                            int32_t* triangle_id, float* depth, float* alpha, float* colour, int32_t* face_pixels,
+                            b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
