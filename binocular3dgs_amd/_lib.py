@@ -176,7 +176,10 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: simplifying an extracted mesh
            "b3gs_mesh_simplify_workspace_bytes", "b3gs_mesh_simplify_count", "b3gs_mesh_simplify_emit",
            # added to ABI 18: rendering an extracted mesh
-           "b3gs_mesh_raster_workspace_bytes", "b3gs_mesh_raster_batch", "b3gs_mesh_resolve_batch")
+           "b3gs_mesh_raster_workspace_bytes", "b3gs_mesh_raster_batch", "b3gs_mesh_resolve_batch",
+           # added to ABI 18: texturing an extracted mesh
+           "b3gs_mesh_texture_atlas_height", "b3gs_mesh_texture_accumulate_batch", "b3gs_mesh_texture_finalize",
+           "b3gs_mesh_resolve_textured_batch")
 
 _lib = None
 
@@ -352,6 +355,14 @@ def lib():
     L.b3gs_mesh_raster_batch.restype = C.c_int
     L.b3gs_mesh_resolve_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, V, V, V, I32, V, V, V, V, V, V]
     L.b3gs_mesh_resolve_batch.restype = C.c_int
+    L.b3gs_mesh_texture_atlas_height.argtypes = [I64, I32, I32]
+    L.b3gs_mesh_texture_atlas_height.restype = I32
+    L.b3gs_mesh_texture_accumulate_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, I32, I32, I32, V, V, V, C.c_float, I32, V, V, V]
+    L.b3gs_mesh_texture_accumulate_batch.restype = C.c_int
+    L.b3gs_mesh_texture_finalize.argtypes = [I32, I64, V, V, I32, I32, I32, V, V, V, V]
+    L.b3gs_mesh_texture_finalize.restype = C.c_int
+    L.b3gs_mesh_resolve_textured_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, V, V, V, I32, I32, I32, V, V, V, V, V, V]
+    L.b3gs_mesh_resolve_textured_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

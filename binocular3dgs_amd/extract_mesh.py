@@ -3,6 +3,8 @@
                                             [--min_weight 1] [--bounds x0 y0 z0 x1 y1 z1]
                                             [--keep_largest 0] [--min_triangles 0] [--cull_unseen [--min_pixels 1]]
                                             [--simplify K | --target_triangles N] [--placement quadric|mean]
+                                            [--texture [--texel_cell N | --atlas_side S] [--texture_from render|gt]
+                                             [--texture_slack X] [--two_sided]]
 
 A triangle mesh of a trained model: the point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply is rendered from
 the chosen cameras, depth, alpha and colour are fused into a TSDF volume and the zero level set is extracted, all on the
@@ -15,6 +17,13 @@ and before the simplification.
 --simplify K clusters the vertices on a grid of K voxels (mesh_tools.simplify), --target_triangles N searches the smallest
 such grid that leaves at most N triangles (mesh_tools.simplify_to); either runs after the cleaning step and prints the counts
 before and after.  --placement says where a cluster's vertex goes: the minimiser of its faces' quadric, or the members' mean.
+--texture bakes the pictures of the cameras of --views into a texture atlas (mesh_texture.bake_texture) and writes mesh.obj,
+mesh.mtl and mesh.png next to mesh.ply; it runs last, on the mesh that mesh.ply holds, and prints the atlas size and the share of
+its texels coloured from the pictures (the others keep the vertex colours).  The pictures are the model's renders
+(--texture_from render, the default) or the cameras' own images (gt, which needs the dataset).  --texel_cell N gives every
+triangle a patch with legs of N - 2 texels; the default is the largest N whose atlas fits a square of --atlas_side (4096)
+texels.  --texture_slack is how far behind the nearest surface a texel may lie and still be seen; the default is one voxel of
+the fusion, or the simplification cell when that is larger: neither resolves two surfaces closer than that.
 
 The model and the cameras are found the way spiral.py finds them: source path, images folder, image resolution, background,
 SH degree, dataset name and view count come from <model_path>/cfg_args; the command line wins.  A model folder whose dataset
@@ -25,6 +34,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -56,6 +66,15 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--placement", choices=("quadric", "mean"), default="quadric", help="where a cluster's vertex goes")
     p.add_argument("--cull_unseen", action="store_true", help="drop the triangles no camera of --views sees")
     p.add_argument("--min_pixels", type=_positive_int, default=1, help="with --cull_unseen: pixels a triangle must win to stay")
+    p.add_argument("--texture", action="store_true", help="also write mesh.obj, mesh.mtl and mesh.png: a texture atlas baked from the views")
+    atlas = p.add_mutually_exclusive_group()
+    atlas.add_argument("--texel_cell", type=_positive_int, default=None, metavar="N", help="with --texture: the cell parameter, 4 .. 256")
+    atlas.add_argument("--atlas_side", type=_positive_int, default=None, metavar="S",
+                       help="with --texture: the largest cell whose atlas fits S x S texels (default 4096)")
+    p.add_argument("--texture_from", choices=("render", "gt"), default="render", help="with --texture: the model's renders or the dataset's images")
+    p.add_argument("--texture_slack", type=float, default=None, metavar="X",
+                   help="with --texture: depth tolerance of the visibility test (default: one voxel, or the simplification cell)")
+    p.add_argument("--two_sided", action="store_true", help="with --texture: a texel also takes the views that see its triangle from behind")
     return p
 
 
@@ -108,7 +127,8 @@ def load_cameras(model_path: str, cfg: dict, source_path, views: str, device="cu
 def run(model_path: str, source_path=None, iteration: int = -1, views: str = "train", resolution=None, voxel_size=None,
         truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, bounds=None,
         keep_largest: int = 0, min_triangles: int = 0, simplify=None, target_triangles=None, placement: str = "quadric",
-        cull_unseen: bool = False, min_pixels: int = 1) -> str:
+        cull_unseen: bool = False, min_pixels: int = 1, texture: bool = False, texel_cell=None, atlas_side=None,
+        texture_from: str = "render", texture_slack=None, two_sided: bool = False) -> str:
     from . import mesh
     from .gaussian_model import GaussianModel
     from .spiral import max_iteration, read_cfg_args
@@ -135,6 +155,7 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
         before = (vertices.shape[0], faces.shape[0])
         vertices, colours, faces = mesh_render.cull_unseen(vertices, colours, faces, cams, min_pixels)
         print(f"culled: {before[1] - faces.shape[0]} of {before[1]} triangles seen by no camera, {before[0] - vertices.shape[0]} vertices")
+    simplify_cell = 0.0
     if simplify is not None or target_triangles is not None:
         from . import mesh_tools
         before = (vertices.shape[0], faces.shape[0])
@@ -145,6 +166,7 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
             vertices, colours, faces, cell = mesh_tools.simplify_to(vertices, colours, faces, target_triangles, placement)
         print(f"simplified ({placement}, cell {cell:g} = {cell / vol.voxel_size:g} voxels): {before[0]} vertices, {before[1]} triangles "
               f"-> {vertices.shape[0]} vertices, {faces.shape[0]} triangles")
+        simplify_cell = float(cell)
     out_dir = os.path.join(model_path, "mesh", "iteration_{}".format(it))
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "mesh.ply")
@@ -153,13 +175,48 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
     nx, ny, nz = vol.dims
     print(f"{len(cams)} views -> {nx} x {ny} x {nz} voxels of {vol.voxel_size:g}: {vertices.shape[0]} vertices, "
           f"{faces.shape[0]} triangles -> {out} in {dt:.2f} s")
+    if texture:
+        slack = max(vol.voxel_size, simplify_cell) if texture_slack is None else texture_slack
+        _write_texture(os.path.join(out_dir, "mesh.obj"), model, cams, bg, vertices, colours, faces, texel_cell, atlas_side, texture_from,
+                       slack, two_sided)
     return out
 
 
+def _write_texture(path, model, cams, bg, vertices, colours, faces, texel_cell, atlas_side, texture_from, slack, two_sided):
+    from . import mesh_texture
+    t0 = time.perf_counter()
+    if faces.shape[0] == 0:
+        raise ValueError("--texture: the mesh has no triangles")
+    if texture_from == "gt":
+        images = [c.original_image for c in cams]
+        if any(im is None for im in images):
+            raise ValueError("--texture_from gt needs the dataset's images: pass -s")
+        images = [im[:3].float().contiguous() for im in images]
+    else:
+        from .evaluate import render_views
+        images = render_views(model, cams, bg)
+    if texel_cell is not None:                                        # about as many cells per row as rows of cells
+        cell, cells = int(texel_cell), (faces.shape[0] + 1) // 2
+        width = min(math.isqrt(cells - 1) + 1, mesh_texture.MAX_SIDE // (cell + 1)) * (cell + 1)
+    else:
+        cell, width = mesh_texture.atlas_for(faces.shape[0], 4096 if atlas_side is None else int(atlas_side))
+    tex, coverage = mesh_texture.bake_texture(vertices, colours, faces, cams, images, cell=cell, width=width, slack=slack, two_sided=two_sided)
+    seen, owned = coverage.tolist()
+    mesh_texture.write_textured_obj(path, vertices, faces, tex, cell)
+    print(f"texture ({texture_from}, slack {slack:g}): cell {cell}, atlas {tex.shape[1]} x {tex.shape[0]}, {seen} of {owned} texels "
+          f"({100.0 * seen / max(owned, 1):.1f} %) coloured from {len(cams)} views -> {path} in {time.perf_counter() - t0:.2f} s")
+
+
 def main(argv=None) -> int:
-    a = parser().parse_args(argv)
+    p = parser()
+    a = p.parse_args(argv)
+    if not a.texture and (a.texel_cell is not None or a.atlas_side is not None or a.texture_from != "render" or a.texture_slack is not None or a.two_sided):
+        p.error("--texel_cell, --atlas_side, --texture_from, --texture_slack and --two_sided need --texture")
+    if a.texture_slack is not None and not (a.texture_slack >= 0.0 and a.texture_slack < float("inf")):
+        p.error("--texture_slack is at least 0 and finite")
     run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
-        a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement, a.cull_unseen, a.min_pixels)
+        a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement, a.cull_unseen, a.min_pixels,
+        a.texture, a.texel_cell, a.atlas_side, a.texture_from, a.texture_slack, a.two_sided)
     return 0
 
 

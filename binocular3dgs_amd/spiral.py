@@ -1,5 +1,5 @@
 """python -m binocular3dgs_amd.spiral -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--resolution R] [--white_background]
-                                      [--video] [--no_png] [--fps 25] [--quality 90] [--mesh MESH.ply [--shading colour|normal]]
+                                      [--video] [--no_png] [--fps 25] [--quality 90] [--mesh MESH.ply|MESH.obj [--shading colour|normal|texture]]
 
 The reference's spiral.py: the trained point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply, rendered along the
 180-frame spiral of <source_path>/poses_bounds.npy (DTU when the source path contains 'scan'), written as %05d.png,
@@ -11,7 +11,9 @@ MP4 files of these names with ffmpeg); --no_png then skips the PNG files.  Witho
 --mesh renders a triangle mesh (the files extract_mesh writes) along the same spiral in place of the model
 (mesh_render.render_mesh; --shading normal shows the face normals), through the same frame and video encoders, into
 <model_path>/render/mesh_<scene>/ and out_mesh_<scene>.avi, out_depth_mesh_<scene>.avi, out_cdepth_mesh_<scene>.avi: the
-model's own outputs are never overwritten, and its point cloud is not read.
+model's own outputs are never overwritten, and its point cloud is not read.  A MESH.obj is the textured mesh
+extract_mesh --texture writes (with its .mtl and .png); it is rendered through its atlas (mesh_texture.batches_textured):
+--shading texture is implied by the extension, and is an error for a .ply.
 
 Defaults for source_path, sh_degree, resolution and white_background come from <model_path>/cfg_args when it exists (the
 Namespace(...) line train.py writes, read with `ast`: literals only, nothing is executed); the command line wins.
@@ -60,7 +62,7 @@ def max_iteration(model_path: str) -> int:
 
 def run(model_path: str, source_path: str = None, iteration: int = -1, resolution=None, white_background=None,
         sh_degree=None, n_frames: int = 180, video: bool = False, png: bool = True, fps: float = 25.0, quality: int = 90,
-        mesh_path: str = None, shading: str = "colour") -> str:
+        mesh_path: str = None, shading: str = None) -> str:
     from . import camera_path, frames
     from .gaussian_model import GaussianModel
     if mesh_path is not None:
@@ -100,20 +102,31 @@ def run(model_path: str, source_path: str = None, iteration: int = -1, resolutio
 
 def _run_mesh(model_path, source_path, resolution, white_background, n_frames, video, png, fps, quality, mesh_path, shading) -> str:
     from . import camera_path, frames, mesh, mesh_render
+    textured = mesh_path.lower().endswith(".obj")
+    if shading is None:
+        shading = "texture" if textured else "colour"
+    if textured != (shading == "texture"):
+        raise ValueError(f"--shading {shading} with {os.path.basename(mesh_path)}: texture goes with a textured .obj, colour and normal with a .ply")
     cfg = read_cfg_args(model_path)
     source_path = source_path or cfg.get("source_path")
     if not source_path:
         raise ValueError("no source path: pass -s or keep cfg_args next to the model")
     resolution = resolution if resolution is not None else cfg.get("resolution", -1)
     white = white_background if white_background is not None else bool(cfg.get("white_background", False))
-    v, c, f = (torch.from_numpy(a).to("cuda") for a in mesh.read_mesh_ply(mesh_path))
+    if textured:
+        from . import mesh_texture
+        hv, hf, htex, cell = mesh_texture.read_textured_obj(mesh_path)
+        v, f, tex = (torch.from_numpy(a).to("cuda") for a in (hv, hf, htex))
+    else:
+        v, c, f = (torch.from_numpy(a).to("cuda") for a in mesh.read_mesh_ply(mesh_path))
     cams = camera_path.spiral_cameras_from_dir(source_path, n_frames=n_frames, resolution=resolution, device="cuda")
     bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
     stem = "mesh_" + os.path.basename(os.path.normpath(source_path))
     out_dir = os.path.join(model_path, "render", stem)
     t0 = time.perf_counter()
+    source = mesh_texture.batches_textured(v, f, tex, cell, cams, bg) if textured else mesh_render.batches(v, c, f, cams, bg, shading=shading)
     res = frames.render_path(None, cams, bg, out_dir, video=(model_path, stem) if video else None, png=png, fps=fps, quality=quality,
-                             source=mesh_render.batches(v, c, f, cams, bg, shading=shading))
+                             source=source)
     dt = time.perf_counter() - t0
     print(f"{len(cams)} frames ({cams[0].image_width}x{cams[0].image_height}) of {f.shape[0]} triangles ({shading}) -> "
           f"{out_dir if png else 'no PNG files'} in {dt:.2f} s")
@@ -136,8 +149,9 @@ def main(argv=None) -> int:
     p.add_argument("--no_png", action="store_true", help="with --video: write no PNG files")
     p.add_argument("--fps", type=float, default=25.0, help="frame rate of the videos (ffmpeg's default for an image sequence)")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality of the video frames, 1..100")
-    p.add_argument("--mesh", default=None, help="render this triangle mesh (PLY) along the spiral in place of the model")
-    p.add_argument("--shading", choices=("colour", "normal"), default="colour", help="with --mesh: vertex colours or face normals")
+    p.add_argument("--mesh", default=None, help="render this triangle mesh (PLY, or a textured OBJ) along the spiral in place of the model")
+    p.add_argument("--shading", choices=("colour", "normal", "texture"), default=None,
+                   help="with --mesh: vertex colours (the default for a .ply), face normals, or the atlas (implied by a .obj)")
     a = p.parse_args(argv)
     if a.no_png and not a.video:
         p.error("--no_png needs --video")

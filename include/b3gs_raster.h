@@ -904,6 +904,79 @@ int b3gs_mesh_resolve_batch(int32_t nviews, const float* cameras, int32_t W, int
                             int32_t* triangle_id, float* depth, float* alpha, float* colour, int32_t* face_pixels,
                             b3gs_stream_t stream);
 
+/* ---- texturing an extracted mesh: atlas bake and textured resolve (ABI 18, added entry points; binocular3dgs_amd/mesh_texture.py,
+ * INTEGRATION.md section 16) -------------------------------------------------------------------------------------------------
+ * Four entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * Every triangle owns a patch of one atlas, texture uint8 [Ht, Wt, 3]; a texel is a point of its triangle's plane, coloured
+ * from up to B3GS_MAX_MESH_VIEWS pictures per call.  Integer layout, single correctly rounded float32 operations (the
+ * translation unit is compiled with -ffp-contract=off), no float atomic and no sum across threads: tests/texture_ref.py restates
+ * every statement in numpy and every output agrees bit for bit, whatever the launch geometry.  Nothing synchronises or reads
+ * the device; the three calls are capturable in a graph.  cameras, W, H, V, F, vertices, faces: as for b3gs_mesh_raster_batch;
+ * F >= 1.
+ *
+ * 1. atlas     cell parameter n, 4 <= n <= 256; a cell is (n + 1) x n texels, local indices i = 0 .. n, j = 0 .. n - 1.
+ *              cpr = Wt / (n + 1) cells per row (integer division, >= 1); cell c = f / 2 of triangle f sits at column c % cpr,
+ *              row c / cpr: its texel (i, j) is texel (x0 + i, y0 + j) of the atlas, x0 = (c % cpr)(n + 1), y0 = (c / cpr) n.
+ *              Ht = n ceil(ceil(F / 2) / cpr) = b3gs_mesh_texture_atlas_height(F, n, Wt) (0: no such atlas); Wt, Ht <= 16384.
+ *              The even triangle 2c owns the texels with i + j <= n - 1, the odd one 2c + 1 those with i + j >= n: n (n + 1) / 2
+ *              each, every texel of the cell once.  The odd half is the even half under i -> n - i, j -> n - 1 - j; (i, j)
+ *              below are the indices in the EVEN frame.  A texel in no cell (x >= cpr (n + 1)) or of a triangle >= F is unowned.
+ *              In texel-centre coordinates (the centre of atlas texel (x, y) is (x, y)) the corners of vertices 0, 1, 2 are
+ *              (x0, y0), (x0 + n - 2, y0), (x0, y0 + n - 2) for the even triangle, and for the odd one
+ *              (x0 + n, y0 + n - 1), (x0 + 2, y0 + n - 1), (x0 + n, y0 + 1).
+ *              Why the legs are n - 2: a bilinear fetch at (u, v) reads texels floor(u), floor(u) + 1 by floor(v), floor(v) + 1,
+ *              the upper ones with weight 0 when u (v) is whole.  In the even frame u, v >= 0 and u + v <= n - 2.  With both
+ *              fractions positive, floor(u) + floor(v) < u + v <= n - 2 is a whole number, so <= n - 3, and the largest index sum
+ *              read is n - 1.  With one fraction positive, say u's, floor(u) + v < n - 2, so <= n - 3, and the texels read have
+ *              sums <= n - 2.  With none, one texel of sum <= n - 2.  Every texel with a weight is owned; legs of n - 1 would
+ *              reach sum n, the other triangle's.  The odd half is the point reflection, which maps such footprints onto each other.
+ *              The owned texels outside the UV triangle (the gutter) are baked like the others, so there is no dilation pass.
+ * 2. texel     b_1 = i / (n - 2), b_2 = j / (n - 2), b_0 = (1 - b_1) - b_2            (negative in the gutter: extrapolation)
+ *              q = (b_0 v0 + b_1 v1) + b_2 v2 per axis, the point of the triangle's plane
+ *              e1 = v1 - v0, e2 = v2 - v0, m = (e1_y e2_z - e1_z e2_y, e1_z e2_x - e1_x e2_z, e1_x e2_y - e1_y e2_x),
+ *              l = sqrt((m_x m_x + m_y m_y) + m_z m_z) (correctly rounded); l = 0 or not finite: the texel takes no view;
+ *              N = m / l per component
+ * 3. accumulate, thread = texel, for the views v = 0 .. nviews - 1 in order (triangle_id int32 [n, H, W], depth float32
+ *    [n, 1, H, W]: the outputs of b3gs_mesh_resolve_batch for the same cameras and mesh; images float32 [n, 3, H, W]):
+ *              p, sx, sy: statement 1 of the mesh rasterizer applied to q
+ *              the view is skipped unless p_2 > 0.2, p_2 is finite, 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (a NaN fails one)
+ *              (i, j) = (rint(sx), rint(sy)), half to even; tid, d = triangle_id, depth there
+ *              visible when tid < 0, or tid = f, or p_2 <= d + slack (one rounded sum); otherwise skipped
+ * 4. weight    C = -((rot[a] t_0 + rot[3 + a] t_1) + rot[6 + a] t_2), a = 0, 1, 2: the camera centre, float32 on the host
+ *              g = C - q, gl = sqrt((g_x g_x + g_y g_y) + g_z g_z); gl = 0 or not finite: skipped
+ *              c = ((N_x g_x + N_y g_y) + N_z g_z) / gl; two_sided: c = |c|; c <= 0 (or NaN): skipped;  w = c c
+ * 5. sample    x0 = floor(sx), fx = sx - x0, gx = 1 - fx, x1 = min(x0 + 1, W - 1); y likewise.  Per channel with
+ *              I the image plane: top = gx I[y0][x0] + fx I[y0][x1], bot = gx I[y1][x0] + fx I[y1][x1], s = gy top + fy bot
+ * 6. sum       accum[texel] = (A_r + w s_r, A_g + w s_g, A_b + w s_b, A_w + w): accum float32 [Ht, Wt, 4], 16-byte aligned, read
+ *              once, carried through the views, written once; the caller zeroes it before the first call and may call again with
+ *              further views.  Unowned texels and the texels of a triangle with an index outside 0 .. V-1 are not touched;
+ *              bad_faces (device int32 [1], zeroed by the call) counts those triangles, once each.  A vertex that is not
+ *              finite gives l, p or gl that is not finite: weight 0.
+ * 7. fetch     the bilinear fetch of statement 5 applies to the atlas as well (W, H -> Wt, Ht; I = the uint8 texel as float).
+ * 8. finalize, thread = texel.  byte(r) = (uint8) rint(255 min(max(r, 0), 1)) (a NaN gives 0).  An owned texel with A_w > 0:
+ *              byte(A_ch / A_w) per channel.  An owned texel with A_w = 0: with c_k = max(b_k, 0), S = (c_0 + c_1) + c_2,
+ *              c_k = c_k / S and C the uint8 vertex colours, byte((((c_0 C_0 + c_1 C_1) + c_2 C_2)) / 255) per channel; 0 when
+ *              colours is NULL or the triangle has an index outside 0 .. V-1.  Unowned texels: 0.
+ *              coverage (device int32 [2], zeroed by the call): [0] = owned texels with A_w > 0, [1] = owned texels.
+ * 9. resolve   b3gs_mesh_resolve_batch (statement 7 there) with the same workspace, the same E_k, b_k, w_k, z, triangle_id,
+ *              depth, alpha and face_pixels; the colour of a covered pixel is, with (U_k, V_k) the corners of its triangle,
+ *              u = ((w_0 U_0 + w_1 U_1) + w_2 U_2) * z, v likewise, u = min(max(u, 0), Wt - 1), v = min(max(v, 0), Ht - 1),
+ *              then statement 7's fetch per channel, divided by 255.  Empty pixels take bg. */
+#define B3GS_TEXTURE_MIN_CELL 4
+#define B3GS_TEXTURE_MAX_CELL 256
+#define B3GS_MAX_ATLAS_SIDE 16384
+int32_t b3gs_mesh_texture_atlas_height(int64_t F, int32_t cell, int32_t Wt);
+int b3gs_mesh_texture_accumulate_batch(int32_t nviews, const float* cameras, int32_t W, int32_t H, int32_t V, int64_t F,
+                                       const float* vertices, const int32_t* faces, int32_t cell, int32_t Wt, int32_t Ht,
+                                       const int32_t* triangle_id, const float* depth, const float* images, float slack,
+                                       int32_t two_sided, float* accum, int32_t* bad_faces, b3gs_stream_t stream);
+int b3gs_mesh_texture_finalize(int32_t V, int64_t F, const uint8_t* colours, const int32_t* faces, int32_t cell, int32_t Wt, int32_t Ht,
+                               const float* accum, uint8_t* texture, int32_t* coverage, b3gs_stream_t stream);
+int b3gs_mesh_resolve_textured_batch(int32_t nviews, const float* cameras, int32_t W, int32_t H, int32_t V, int64_t F,
+                                     const float* vertices, const int32_t* faces, const void* workspace, const float* bg,
+                                     const uint8_t* texture, int32_t cell, int32_t Wt, int32_t Ht, int32_t* triangle_id, float* depth,
+                                     float* alpha, float* colour, int32_t* face_pixels, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
