@@ -179,7 +179,10 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_mesh_raster_workspace_bytes", "b3gs_mesh_raster_batch", "b3gs_mesh_resolve_batch",
            # added to ABI 18: texturing an extracted mesh
            "b3gs_mesh_texture_atlas_height", "b3gs_mesh_texture_accumulate_batch", "b3gs_mesh_texture_finalize",
-           "b3gs_mesh_resolve_textured_batch")
+           "b3gs_mesh_resolve_textured_batch",
+           # added to ABI 18: smoothing an extracted mesh
+           "b3gs_mesh_adjacency_workspace_bytes", "b3gs_mesh_adjacency_layout", "b3gs_mesh_adjacency_build", "b3gs_mesh_smooth",
+           "b3gs_mesh_vertex_normals", "b3gs_mesh_resolve_shaded_batch")
 
 _lib = None
 
@@ -363,6 +366,18 @@ def lib():
     L.b3gs_mesh_texture_finalize.restype = C.c_int
     L.b3gs_mesh_resolve_textured_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, V, V, V, I32, I32, I32, V, V, V, V, V, V]
     L.b3gs_mesh_resolve_textured_batch.restype = C.c_int
+    L.b3gs_mesh_adjacency_workspace_bytes.argtypes = [I64, I64]
+    L.b3gs_mesh_adjacency_workspace_bytes.restype = C.c_size_t
+    L.b3gs_mesh_adjacency_layout.argtypes = [I64, I64, C.POINTER(C.c_size_t)]
+    L.b3gs_mesh_adjacency_layout.restype = C.c_int
+    L.b3gs_mesh_adjacency_build.argtypes = [I32, I64, V, V, V, V]
+    L.b3gs_mesh_adjacency_build.restype = C.c_int
+    L.b3gs_mesh_smooth.argtypes = [I32, I64, V, V, I32, C.c_double, C.c_double, I32, V, V]
+    L.b3gs_mesh_smooth.restype = C.c_int
+    L.b3gs_mesh_vertex_normals.argtypes = [I32, I64, V, V, V, V, V]
+    L.b3gs_mesh_vertex_normals.restype = C.c_int
+    L.b3gs_mesh_resolve_shaded_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, V, V, I32, V, V, V, V, V, V]
+    L.b3gs_mesh_resolve_shaded_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -80,5 +80,6 @@ void bind_meshtools(pybind11::module_& m);
 void bind_simplify(pybind11::module_& m);
 void bind_meshraster(pybind11::module_& m);
 void bind_texture(pybind11::module_& m);
+void bind_meshsmooth(pybind11::module_& m);
 
 }  // namespace b3

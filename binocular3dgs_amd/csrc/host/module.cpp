@@ -58,4 +58,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_simplify(m);
   b3::bind_meshraster(m);
   b3::bind_texture(m);
+  b3::bind_meshsmooth(m);
 }

@@ -5,8 +5,9 @@
 Scores a triangle mesh (the files mesh.write_mesh_ply writes) against a reference point cloud (any PLY whose vertex element
 has x, y, z), on the device: the mesh is optionally cleaned (mesh_tools.clean), sampled at `spacing` (the vertices plus a
 lattice per triangle) and compared with the cloud both ways by nearest point-to-point distance capped at `max_dist`:
-accuracy, completeness, chamfer, and precision, recall and F-score at `tau`.  Prints the dict and writes mesh_results.json
-next to the mesh.
+accuracy, completeness, chamfer, and precision, recall and F-score at `tau`.  Prints the topology line of the mesh as read
+(mesh_tools.topology: edges, boundary and non-manifold edges, Euler characteristic), then the dict, and writes
+mesh_results.json next to the mesh.
 
 With -m the mesh is also rendered into the model's cameras (extract_mesh's way of finding them) and compared with the model's
 own rendered depth there (mesh_render.depth_agreement): the dict goes into the result as "depth_agreement".
@@ -50,6 +51,7 @@ def run(mesh_path: str, gt_path: str, spacing: float, max_dist: float, tau: floa
     rows = read_ply_vertices(gt_path)
     gt = torch.from_numpy(np.stack([rows["x"], rows["y"], rows["z"]], axis=1).astype(np.float32)).to(device)
     vertices, colours, faces = torch.from_numpy(v).to(device), torch.from_numpy(c).to(device), torch.from_numpy(f).to(device)
+    print(mesh_tools.topology_line(mesh_tools.topology(vertices, faces)))
     if keep_largest or min_triangles:
         vertices, colours, faces = mesh_tools.clean(vertices, colours, faces, keep_largest, min_triangles)
     result = mesh_tools.score_mesh(vertices, faces, gt, spacing, max_dist, tau)

@@ -2,6 +2,7 @@
                                             [--resolution 256 | --voxel_size S] [--truncation_voxels 4] [--alpha_min 0.5]
                                             [--min_weight 1] [--bounds x0 y0 z0 x1 y1 z1]
                                             [--keep_largest 0] [--min_triangles 0] [--cull_unseen [--min_pixels 1]]
+                                            [--smooth N [--smooth_lambda 0.5] [--smooth_mu -0.53] [--free_boundary]] [--normals]
                                             [--simplify K | --target_triangles N] [--placement quadric|mean]
                                             [--texture [--texel_cell N | --atlas_side S] [--texture_from render|gt]
                                              [--texture_slack X] [--two_sided]]
@@ -14,6 +15,11 @@ all survive), --min_triangles M the components with at least M (mesh_tools.clean
 --cull_unseen renders the mesh into the cameras of --views (mesh_render.cull_unseen) and drops the triangles that win fewer
 than --min_pixels pixels over all of them, e.g. blobs inside or behind the observed surface; it runs after the cleaning step
 and before the simplification.
+--smooth N runs N iterations of Taubin's filter on the vertices (mesh_tools.smooth: pairs of steps with --smooth_lambda and
+--smooth_mu, mu < -lambda, or mu = 0 for a plain Laplacian filter); it runs after --cull_unseen and before the simplification,
+keeps the ends of boundary and non-manifold edges in place unless --free_boundary is given, and prints the vertex count, the
+step count and the topology line (mesh_tools.topology).  --normals computes area-weighted vertex normals of the final mesh
+(mesh_tools.vertex_normals) and writes them into mesh.ply as nx ny nz.
 --simplify K clusters the vertices on a grid of K voxels (mesh_tools.simplify), --target_triangles N searches the smallest
 such grid that leaves at most N triangles (mesh_tools.simplify_to); either runs after the cleaning step and prints the counts
 before and after.  --placement says where a cluster's vertex goes: the minimiser of its faces' quadric, or the members' mean.
@@ -66,6 +72,12 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--placement", choices=("quadric", "mean"), default="quadric", help="where a cluster's vertex goes")
     p.add_argument("--cull_unseen", action="store_true", help="drop the triangles no camera of --views sees")
     p.add_argument("--min_pixels", type=_positive_int, default=1, help="with --cull_unseen: pixels a triangle must win to stay")
+    p.add_argument("--smooth", type=_positive_int, default=None, metavar="N", help="N iterations of Taubin's filter before the simplification")
+    p.add_argument("--smooth_lambda", type=float, default=None, metavar="L", help="with --smooth: the shrinking factor, in (0, 1] (default 0.5)")
+    p.add_argument("--smooth_mu", type=float, default=None, metavar="M",
+                   help="with --smooth: the inflating factor, below -lambda, or 0 for a plain Laplacian filter (default -0.53)")
+    p.add_argument("--free_boundary", action="store_true", help="with --smooth: boundary and non-manifold vertices move too")
+    p.add_argument("--normals", action="store_true", help="write area-weighted vertex normals into mesh.ply")
     p.add_argument("--texture", action="store_true", help="also write mesh.obj, mesh.mtl and mesh.png: a texture atlas baked from the views")
     atlas = p.add_mutually_exclusive_group()
     atlas.add_argument("--texel_cell", type=_positive_int, default=None, metavar="N", help="with --texture: the cell parameter, 4 .. 256")
@@ -128,7 +140,8 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
         truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, bounds=None,
         keep_largest: int = 0, min_triangles: int = 0, simplify=None, target_triangles=None, placement: str = "quadric",
         cull_unseen: bool = False, min_pixels: int = 1, texture: bool = False, texel_cell=None, atlas_side=None,
-        texture_from: str = "render", texture_slack=None, two_sided: bool = False) -> str:
+        texture_from: str = "render", texture_slack=None, two_sided: bool = False, smooth=None, smooth_lambda: float = 0.5,
+        smooth_mu: float = -0.53, free_boundary: bool = False, normals: bool = False) -> str:
     from . import mesh
     from .gaussian_model import GaussianModel
     from .spiral import max_iteration, read_cfg_args
@@ -155,6 +168,14 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
         before = (vertices.shape[0], faces.shape[0])
         vertices, colours, faces = mesh_render.cull_unseen(vertices, colours, faces, cams, min_pixels)
         print(f"culled: {before[1] - faces.shape[0]} of {before[1]} triangles seen by no camera, {before[0] - vertices.shape[0]} vertices")
+    if smooth is not None:
+        from . import mesh_tools
+        adj = mesh_tools.adjacency(vertices, faces)
+        vertices = mesh_tools.smooth(vertices, faces, smooth, smooth_lambda, smooth_mu, not free_boundary, adjacency=adj)
+        steps = smooth * (2 if smooth_mu != 0.0 else 1)
+        print(f"smoothed: {vertices.shape[0]} vertices, {steps} steps (lambda {smooth_lambda:g}, mu {smooth_mu:g}, "
+              f"boundary {'free' if free_boundary else 'pinned'})")
+        print(mesh_tools.topology_line(mesh_tools.topology(vertices, faces, adjacency=adj)))
     simplify_cell = 0.0
     if simplify is not None or target_triangles is not None:
         from . import mesh_tools
@@ -170,7 +191,11 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
     out_dir = os.path.join(model_path, "mesh", "iteration_{}".format(it))
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "mesh.ply")
-    mesh.write_mesh_ply(out, vertices, colours, faces)
+    if normals:
+        from . import mesh_tools
+        mesh.write_mesh_ply(out, vertices, colours, faces, mesh_tools.vertex_normals(vertices, faces))
+    else:
+        mesh.write_mesh_ply(out, vertices, colours, faces)
     dt = time.perf_counter() - t0
     nx, ny, nz = vol.dims
     print(f"{len(cams)} views -> {nx} x {ny} x {nz} voxels of {vol.voxel_size:g}: {vertices.shape[0]} vertices, "
@@ -212,11 +237,19 @@ def main(argv=None) -> int:
     a = p.parse_args(argv)
     if not a.texture and (a.texel_cell is not None or a.atlas_side is not None or a.texture_from != "render" or a.texture_slack is not None or a.two_sided):
         p.error("--texel_cell, --atlas_side, --texture_from, --texture_slack and --two_sided need --texture")
+    if a.smooth is None and (a.smooth_lambda is not None or a.smooth_mu is not None or a.free_boundary):
+        p.error("--smooth_lambda, --smooth_mu and --free_boundary need --smooth")
+    lam = 0.5 if a.smooth_lambda is None else a.smooth_lambda
+    mu = -0.53 if a.smooth_mu is None else a.smooth_mu
+    if not (0.0 < lam <= 1.0):
+        p.error("--smooth_lambda is in (0, 1]")
+    if not (mu == 0.0 or mu < -lam):
+        p.error("--smooth_mu is below -lambda, or 0")
     if a.texture_slack is not None and not (a.texture_slack >= 0.0 and a.texture_slack < float("inf")):
         p.error("--texture_slack is at least 0 and finite")
     run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
         a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement, a.cull_unseen, a.min_pixels,
-        a.texture, a.texel_cell, a.atlas_side, a.texture_from, a.texture_slack, a.two_sided)
+        a.texture, a.texel_cell, a.atlas_side, a.texture_from, a.texture_slack, a.two_sided, a.smooth, lam, mu, a.free_boundary, a.normals)
     return 0
 
 

@@ -148,7 +148,12 @@ def fuse_model(model, cameras: Sequence, bg: torch.Tensor, *, resolution: Option
 
 # ---- PLY ---------------------------------------------------------------------------------------------------------------
 _VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_VERTEX_N = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                      ("red", "u1"), ("green", "u1"), ("blue", "u1")])                       # with vertex normals
 _FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+_PROPS = ["property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+          "property uchar blue", "property list uchar int vertex_indices"]
+_PROPS_N = _PROPS[:3] + ["property float nx", "property float ny", "property float nz"] + _PROPS[3:]
 
 
 def _host(a, dtype):
@@ -157,17 +162,24 @@ def _host(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def write_mesh_ply(path: str, vertices, colours, faces) -> None:
-    """Binary little-endian PLY: x y z (float32) red green blue (uint8) per vertex, `list uchar int vertex_indices` per face."""
+def write_mesh_ply(path: str, vertices, colours, faces, normals=None) -> None:
+    """Binary little-endian PLY: x y z (float32) red green blue (uint8) per vertex, `list uchar int vertex_indices` per face.
+    With normals (float32 [V, 3]) the vertex also carries nx ny nz (float32) after x y z; without them the bytes are unchanged."""
     v, c, f = _host(vertices, np.float32).reshape(-1, 3), _host(colours, np.uint8).reshape(-1, 3), _host(faces, np.int32).reshape(-1, 3)
     if len(v) != len(c):
         raise ValueError("write_mesh_ply: one colour per vertex")
+    nrm = None if normals is None else _host(normals, np.float32).reshape(-1, 3)
+    if nrm is not None and len(nrm) != len(v):
+        raise ValueError("write_mesh_ply: one normal per vertex")
     header = ("ply\nformat binary_little_endian 1.0\n"
               f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              + ("" if nrm is None else "property float nx\nproperty float ny\nproperty float nz\n") +
               "property uchar red\nproperty uchar green\nproperty uchar blue\n"
               f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
-    vr = np.empty(len(v), dtype=_VERTEX)
+    vr = np.empty(len(v), dtype=_VERTEX if nrm is None else _VERTEX_N)
     vr["x"], vr["y"], vr["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if nrm is not None:
+        vr["nx"], vr["ny"], vr["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     vr["red"], vr["green"], vr["blue"] = c[:, 0], c[:, 1], c[:, 2]
     fr = np.empty(len(f), dtype=_FACE)
     fr["n"] = 3
@@ -178,8 +190,10 @@ def write_mesh_ply(path: str, vertices, colours, faces) -> None:
         fp.write(fr.tobytes())
 
 
-def read_mesh_ply(path: str):
-    """The files write_mesh_ply writes -> (vertices float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) numpy arrays."""
+def read_mesh_ply(path: str, return_normals: bool = False):
+    """The files write_mesh_ply writes -> (vertices float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) numpy arrays, with or
+    without vertex normals in the file; return_normals adds a fourth item, the normals float32 [V,3] or None when the file has
+    none."""
     with open(path, "rb") as fp:
         data = fp.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -188,14 +202,20 @@ def read_mesh_ply(path: str):
         raise ValueError(f"{path}: not a binary little-endian PLY")
     counts = {ln.split()[1]: int(ln.split()[2]) for ln in lines if ln.startswith("element ")}
     props = [ln for ln in lines if ln.startswith("property ")]
-    if props != ["property float x", "property float y", "property float z", "property uchar red", "property uchar green",
-                 "property uchar blue", "property list uchar int vertex_indices"]:
+    if props not in (_PROPS, _PROPS_N):
         raise ValueError(f"{path}: not the layout write_mesh_ply writes")
+    vertex = _VERTEX_N if props == _PROPS_N else _VERTEX
     nv, nf = counts["vertex"], counts["face"]
-    vr = np.frombuffer(data, dtype=_VERTEX, count=nv, offset=end)
-    fr = np.frombuffer(data, dtype=_FACE, count=nf, offset=end + nv * _VERTEX.itemsize)
+    vr = np.frombuffer(data, dtype=vertex, count=nv, offset=end)
+    fr = np.frombuffer(data, dtype=_FACE, count=nf, offset=end + nv * vertex.itemsize)
     if nf and not (fr["n"] == 3).all():
         raise ValueError(f"{path}: a face is not a triangle")
     vertices = np.stack([vr["x"], vr["y"], vr["z"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
     colours = np.stack([vr["red"], vr["green"], vr["blue"]], axis=1).astype(np.uint8) if nv else np.zeros((0, 3), np.uint8)
-    return vertices, colours, np.array(fr["v"], dtype=np.int32).reshape(-1, 3)
+    faces = np.array(fr["v"], dtype=np.int32).reshape(-1, 3)
+    if not return_normals:
+        return vertices, colours, faces
+    normals = None
+    if vertex is _VERTEX_N:
+        normals = np.stack([vr["nx"], vr["ny"], vr["nz"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+    return vertices, colours, faces, normals

@@ -2,6 +2,7 @@
 INTEGRATION.md section 15).
 
     outs, rejected = render_mesh(vertices, colours, faces, cameras, bg, shading="colour")
+    outs, rejected = render_mesh_shaded(vertices, normals, faces, cameras, bg, mode="lit")     # vertex normals: "smooth" or "lit"
     counts = face_pixels(vertices, faces, cameras)                       # int32 [F]: pixels each triangle wins, no host read
     vertices, colours, faces = cull_unseen(vertices, colours, faces, cameras, min_pixels=1)
     stats = depth_agreement(model, vertices, faces, cameras, bg)         # the mesh against the model's own rendered depth
@@ -28,6 +29,7 @@ MAX_IMAGE = 16384          # pixels per side (B3GS_MAX_MESH_IMAGE)
 SMALL_BOX = 32             # a clamped box of at most this many pixels is walked by one lane (B3GS_MESH_SMALL_BOX)
 WAVE_BOX = 4096            # ... of at most this many by one wave, beyond by one workgroup (B3GS_MESH_WAVE_BOX)
 SHADINGS = {"colour": 0, "normal": 1}      # B3GS_MESH_SHADE_COLOUR / _NORMAL
+SHADED = {"smooth": 2, "lit": 3}           # B3GS_MESH_SHADE_SMOOTH / _LIT: the modes of render_mesh_shaded (vertex normals)
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -130,6 +132,62 @@ def batches(vertices, colours, faces, cameras, bg=None, *, shading="colour", cul
     for start, end, W, H in runs:
         tid, depth, alpha, colour, _ = raster_views(vertices, colours, faces, table[start:end], W, H, bg, shading=shading,
                                                     cull_backface=cull_backface)
+        yield list(range(start, end)), [{"render": colour[k], "rendered_depth": depth[k], "rendered_alpha": alpha[k], "triangle_id": tid[k]}
+                                        for k in range(end - start)]
+
+
+# ---- shading from vertex normals (csrc/meshsmooth.hip) -------------------------------------------------
+def _check_normals(vertices, normals, mode, what):
+    if mode not in SHADED:
+        raise ValueError(f"{what}: mode is one of {sorted(SHADED)}")
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != tuple(vertices.shape):
+        raise ValueError(f"{what}: normals are float32 [V, 3], one per vertex")
+    if normals.device != vertices.device:
+        raise ValueError(f"{what}: normals are on {normals.device}, vertices on {vertices.device}")
+
+
+def raster_views_shaded(vertices, normals, faces, table, W, H, bg=None, *, mode="smooth", cull_backface=False, face_pixels=None,
+                        small_box=-1, wave_box=-1):
+    """raster_views with the colour taken from the vertex normals (mesh_tools.vertex_normals), interpolated perspective-correctly:
+    "smooth" shows the unit normal in camera space, turned to the camera, as (n + 1) / 2; "lit" a grey headlight,
+    0.15 + 0.85 max(-n_z, 0).  The other outputs are those of raster_views, bit for bit.  No host read."""
+    from . import _C
+    if mode not in SHADED:
+        raise ValueError(f"mesh_render: mode is one of {sorted(SHADED)}")
+    table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 14))
+    if not 1 <= table.shape[0] <= MAX_VIEWS:
+        raise ValueError(f"mesh_render: 1 .. {MAX_VIEWS} views per launch")
+    ws, counts = _C.mesh_raster(vertices, faces, table, W, H, bool(cull_backface), int(small_box), int(wave_box))
+    tid, depth, alpha, colour = _C.mesh_resolve_shaded(normals, faces, table, W, H, ws, bg, SHADED[mode], face_pixels)
+    return tid, depth, alpha, colour, counts
+
+
+def render_mesh_shaded(vertices: torch.Tensor, normals: torch.Tensor, faces: torch.Tensor, cameras, bg: Optional[torch.Tensor] = None, *,
+                       mode: str = "smooth", cull_backface: bool = False, size=None):
+    """render_mesh with the shading of raster_views_shaded -> (per view output dicts, rejected), the shapes of render_mesh."""
+    _check_mesh(vertices, None, faces, "render_mesh_shaded")
+    _check_normals(vertices, normals, mode, "render_mesh_shaded")
+    table, runs = _camera_runs(cameras, size, "render_mesh_shaded")
+    outs: List[dict] = []
+    rejected = torch.zeros(len(table) + 1, dtype=torch.int32, device=vertices.device)
+    for start, end, W, H in runs:
+        tid, depth, alpha, colour, counts = raster_views_shaded(vertices, normals, faces, table[start:end], W, H, bg, mode=mode,
+                                                                cull_backface=cull_backface)
+        rejected[start:end] = counts[:end - start]
+        rejected[-1:] = counts[MAX_VIEWS:]
+        for k in range(end - start):
+            outs.append({"render": colour[k], "rendered_depth": depth[k], "rendered_alpha": alpha[k], "triangle_id": tid[k]})
+    return outs, rejected
+
+
+def batches_shaded(vertices, normals, faces, cameras, bg=None, *, mode="smooth", cull_backface=False, size=None):
+    """batches with the shading of raster_views_shaded: the per-batch source frames.render_path takes."""
+    _check_mesh(vertices, None, faces, "mesh_render.batches_shaded")
+    _check_normals(vertices, normals, mode, "mesh_render.batches_shaded")
+    table, runs = _camera_runs(cameras, size, "mesh_render.batches_shaded")
+    for start, end, W, H in runs:
+        tid, depth, alpha, colour, _ = raster_views_shaded(vertices, normals, faces, table[start:end], W, H, bg, mode=mode,
+                                                           cull_backface=cull_backface)
         yield list(range(start, end)), [{"render": colour[k], "rendered_depth": depth[k], "rendered_alpha": alpha[k], "triangle_id": tid[k]}
                                         for k in range(end - start)]
 

@@ -9,8 +9,13 @@ csrc/simplify.hip).
     score = score_mesh(vertices, faces, gt, spacing, max_dist, tau)
     vertices, colours, faces = simplify(vertices, colours, faces, cell, placement="quadric")     # vertex clustering
     vertices, colours, faces, cell = simplify_to(vertices, colours, faces, target_triangles)
+    adj = adjacency(vertices, faces)                                     # the vertex adjacency, built once per set of faces
+    vertices = smooth(vertices, faces, iterations=10, adjacency=adj)     # Taubin filter (csrc/meshsmooth.hip, section 17)
+    normals = vertex_normals(vertices, faces, adjacency=adj)             # float32 [V, 3], area-weighted
+    info = topology(vertices, faces, adjacency=adj)                      # edges, boundary, non-manifold, euler, closed
 
-The arithmetic is stated in include/b3gs_raster.h and restated in numpy by tests/meshtools_ref.py and tests/simplify_ref.py.  Policy that is not hot
+The arithmetic is stated in include/b3gs_raster.h and restated in numpy by tests/meshtools_ref.py, tests/simplify_ref.py and
+tests/meshsmooth_ref.py.  Policy that is not hot
 lives here in torch: the component threshold of `clean` (a topk of the triangle counts, kept on the device).
 
 The score is the point-to-point measure of the DTU surface benchmark (distances both ways between points on the
@@ -262,3 +267,118 @@ def simplify_to(vertices: torch.Tensor, colours: torch.Tensor, faces: torch.Tens
         raise ValueError("simplify_to: the vertices span no finite, positive extent")
     cell, _ = bisect_cell(lambda c: _simplify_count(vertices, faces, c, "simplify_to")[1][1], extent, int(target_triangles))
     return simplify(vertices, colours, faces, cell, placement) + (cell,)
+
+
+# ---- smoothing: vertex adjacency, Taubin filter, vertex normals (csrc/meshsmooth.hip) -----------------------------------------
+TOTALS = ("bad_faces", "nonfinite_vertices", "edges", "boundary_edges", "non_manifold_edges", "pinned_vertices", "isolated_vertices",
+          "good_faces")     # the eight int64 words at the head of the adjacency workspace, in order
+
+
+def _check_smooth_mesh(vertices, faces, what):
+    if not isinstance(vertices, torch.Tensor) or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"{what}: vertices are float32 [V, 3]")
+    if not isinstance(faces, torch.Tensor) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces are int32 [F, 3]")
+    if vertices.shape[0] > 2 ** 31 - 1 or 6 * faces.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f"{what}: V <= 2^31 - 1 and 6 F <= 2^31 - 1")
+
+
+class Adjacency:
+    """The built adjacency workspace of one mesh (opaque; reusable while the faces are unchanged): per vertex its neighbours in
+    ascending order and its faces in face-index order, the edge classes and the totals, all on the device.  `totals` is the
+    int64 [8] device view of TOTALS; lists() gives views of the lists (what the tests compare).  Nothing here reads the device
+    except check()."""
+
+    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor):
+        from . import _C
+        _check_smooth_mesh(vertices, faces, "adjacency")
+        self.V, self.F = int(vertices.shape[0]), int(faces.shape[0])
+        self.workspace = _C.mesh_adjacency_build(vertices, faces)
+        self.totals = _C.mesh_adjacency_views(self.workspace, self.V, self.F)[0]
+
+    def lists(self) -> dict:
+        """Device views: neighbour_offsets int32 [V + 1], neighbour_indices int32 [6 F] (the first offsets[V] are meaningful),
+        incidence_ranges int32 [V, 2], incident_faces int32 [3 F], pinned uint8 [V]."""
+        from . import _C
+        _, off, idx, rng, inc, pinned = _C.mesh_adjacency_views(self.workspace, self.V, self.F)
+        return {"neighbour_offsets": off, "neighbour_indices": idx, "incidence_ranges": rng, "incident_faces": inc, "pinned": pinned}
+
+    def matches(self, vertices, faces) -> bool:
+        return self.V == int(vertices.shape[0]) and self.F == int(faces.shape[0]) and self.workspace.device == vertices.device
+
+    def check(self, what: str) -> list:
+        """The ONE host read: the totals -> the list, ValueError for bad faces or vertices that are not finite."""
+        t = self.totals.tolist()
+        if t[0]:
+            raise ValueError(f"{what}: {t[0]} triangles name a vertex outside 0 .. {self.V - 1}")
+        if t[1]:
+            raise ValueError(f"{what}: {t[1]} vertices have a coordinate that is not finite")
+        return t
+
+
+def adjacency(vertices: torch.Tensor, faces: torch.Tensor) -> Adjacency:
+    """Builds the vertex adjacency of the mesh on the device -> an opaque holder that smooth, vertex_normals and topology take.
+    No host read (capturable)."""
+    return Adjacency(vertices, faces)
+
+
+def _adjacency_for(vertices, faces, adj, what) -> Adjacency:
+    _check_smooth_mesh(vertices, faces, what)
+    if adj is None:
+        return Adjacency(vertices, faces)
+    if not isinstance(adj, Adjacency) or not adj.matches(vertices, faces):
+        raise ValueError(f"{what}: the adjacency was built for another mesh ({getattr(adj, 'V', '?')} vertices, {getattr(adj, 'F', '?')} triangles)")
+    return adj
+
+
+def smooth(vertices: torch.Tensor, faces: torch.Tensor, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, pin_boundary: bool = True,
+           adjacency: Optional[Adjacency] = None, *, check: bool = True) -> torch.Tensor:
+    """Taubin's filter: `iterations` pairs of Jacobi steps x_i += k (mean of the neighbours - x_i), k = lam then k = mu (mu < -lam,
+    which keeps the volume; mu = 0 is the plain Laplacian filter of `iterations` steps, which shrinks) -> float32 [V, 3];
+    colours and faces are the caller's and unchanged.  pin_boundary keeps the ends of boundary and non-manifold edges where they
+    are.  Neighbour sums are fp64 in ascending neighbour order, without atomics: one fixed result.  Errors, not clamps: a face
+    index outside 0 .. V-1, a coordinate that is not finite (one host read, after the kernels have run; check=False skips it,
+    e.g. under graph capture, and leaves the counts in adjacency.totals)."""
+    from . import _C
+    if iterations < 0:
+        raise ValueError("smooth: iterations is not negative")
+    if not (0.0 < lam <= 1.0):
+        raise ValueError("smooth: lam is in (0, 1]")
+    if mu > 0.0 or mu != mu:
+        raise ValueError("smooth: mu is not positive")
+    if mu != 0.0 and mu >= -lam:
+        raise ValueError("smooth: Taubin's condition is mu < -lam (or mu = 0 for the Laplacian filter)")
+    adj = _adjacency_for(vertices, faces, adjacency, "smooth")
+    out = _C.mesh_smooth(vertices, adj.F, adj.workspace, int(iterations), float(lam), float(mu), bool(pin_boundary))
+    if check:
+        adj.check("smooth")
+    return out
+
+
+def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, adjacency: Optional[Adjacency] = None, *, check: bool = True) -> torch.Tensor:
+    """float32 [V, 3]: per vertex the unit sum of its faces' normals (p1 - p0) x (p2 - p0), i.e. area-weighted, summed in fp64 in
+    face-index order; (0, 0, 0) for a vertex without faces or with a sum of length 0.  check: as for smooth."""
+    from . import _C
+    adj = _adjacency_for(vertices, faces, adjacency, "vertex_normals")
+    out = _C.mesh_vertex_normals(vertices, faces, adj.workspace)
+    if check:
+        adj.check("vertex_normals")
+    return out
+
+
+def topology(vertices: torch.Tensor, faces: torch.Tensor, adjacency: Optional[Adjacency] = None) -> dict:
+    """The totals of the adjacency (TOTALS) and euler = (V - isolated) - E + good faces, closed = no boundary and no non-manifold
+    edge.  One host read.  nonfinite_vertices describes the vertices of the latest call that used the adjacency."""
+    adj = _adjacency_for(vertices, faces, adjacency, "topology")
+    t = adj.totals.tolist()                                               # the one host read
+    out = dict(zip(TOTALS, t))
+    out["vertices"], out["triangles"] = adj.V, adj.F
+    out["euler"] = (adj.V - out["isolated_vertices"]) - out["edges"] + out["good_faces"]
+    out["closed"] = out["boundary_edges"] == 0 and out["non_manifold_edges"] == 0
+    return out
+
+
+def topology_line(info: dict) -> str:
+    """The line the command lines print for topology()"""
+    return (f"topology: {info['vertices']} vertices ({info['isolated_vertices']} isolated), {info['edges']} edges ({info['boundary_edges']} boundary, "
+            f"{info['non_manifold_edges']} non-manifold), {info['good_faces']} triangles, euler {info['euler']}, {'closed' if info['closed'] else 'open'}")

@@ -1,5 +1,5 @@
 """python -m binocular3dgs_amd.spiral -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--resolution R] [--white_background]
-                                      [--video] [--no_png] [--fps 25] [--quality 90] [--mesh MESH.ply|MESH.obj [--shading colour|normal|texture]]
+                                      [--video] [--no_png] [--fps 25] [--quality 90] [--mesh MESH.ply|MESH.obj [--shading colour|normal|smooth|lit|texture]]
 
 The reference's spiral.py: the trained point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply, rendered along the
 180-frame spiral of <source_path>/poses_bounds.npy (DTU when the source path contains 'scan'), written as %05d.png,
@@ -13,7 +13,9 @@ MP4 files of these names with ffmpeg); --no_png then skips the PNG files.  Witho
 <model_path>/render/mesh_<scene>/ and out_mesh_<scene>.avi, out_depth_mesh_<scene>.avi, out_cdepth_mesh_<scene>.avi: the
 model's own outputs are never overwritten, and its point cloud is not read.  A MESH.obj is the textured mesh
 extract_mesh --texture writes (with its .mtl and .png); it is rendered through its atlas (mesh_texture.batches_textured):
---shading texture is implied by the extension, and is an error for a .ply.
+--shading texture is implied by the extension, and is an error for a .ply.  --shading smooth and lit shade a .ply from its
+vertex normals (mesh_render.batches_shaded: the interpolated normal as a colour, or a grey headlight); the normals are those of
+the file (extract_mesh --normals) and are computed on load (mesh_tools.vertex_normals) when it has none.
 
 Defaults for source_path, sh_degree, resolution and white_background come from <model_path>/cfg_args when it exists (the
 Namespace(...) line train.py writes, read with `ast`: literals only, nothing is executed); the command line wins.
@@ -106,7 +108,7 @@ def _run_mesh(model_path, source_path, resolution, white_background, n_frames, v
     if shading is None:
         shading = "texture" if textured else "colour"
     if textured != (shading == "texture"):
-        raise ValueError(f"--shading {shading} with {os.path.basename(mesh_path)}: texture goes with a textured .obj, colour and normal with a .ply")
+        raise ValueError(f"--shading {shading} with {os.path.basename(mesh_path)}: texture goes with a textured .obj, colour, normal, smooth and lit with a .ply")
     cfg = read_cfg_args(model_path)
     source_path = source_path or cfg.get("source_path")
     if not source_path:
@@ -118,13 +120,22 @@ def _run_mesh(model_path, source_path, resolution, white_background, n_frames, v
         hv, hf, htex, cell = mesh_texture.read_textured_obj(mesh_path)
         v, f, tex = (torch.from_numpy(a).to("cuda") for a in (hv, hf, htex))
     else:
-        v, c, f = (torch.from_numpy(a).to("cuda") for a in mesh.read_mesh_ply(mesh_path))
+        hv, hc, hf, hn = mesh.read_mesh_ply(mesh_path, return_normals=True)
+        v, c, f = (torch.from_numpy(a).to("cuda") for a in (hv, hc, hf))
+        if shading in mesh_render.SHADED:
+            from . import mesh_tools
+            nrm = mesh_tools.vertex_normals(v, f) if hn is None else torch.from_numpy(hn).to("cuda")
     cams = camera_path.spiral_cameras_from_dir(source_path, n_frames=n_frames, resolution=resolution, device="cuda")
     bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
     stem = "mesh_" + os.path.basename(os.path.normpath(source_path))
     out_dir = os.path.join(model_path, "render", stem)
     t0 = time.perf_counter()
-    source = mesh_texture.batches_textured(v, f, tex, cell, cams, bg) if textured else mesh_render.batches(v, c, f, cams, bg, shading=shading)
+    if textured:
+        source = mesh_texture.batches_textured(v, f, tex, cell, cams, bg)
+    elif shading in mesh_render.SHADED:
+        source = mesh_render.batches_shaded(v, nrm, f, cams, bg, mode=shading)
+    else:
+        source = mesh_render.batches(v, c, f, cams, bg, shading=shading)
     res = frames.render_path(None, cams, bg, out_dir, video=(model_path, stem) if video else None, png=png, fps=fps, quality=quality,
                              source=source)
     dt = time.perf_counter() - t0
@@ -150,8 +161,9 @@ def main(argv=None) -> int:
     p.add_argument("--fps", type=float, default=25.0, help="frame rate of the videos (ffmpeg's default for an image sequence)")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality of the video frames, 1..100")
     p.add_argument("--mesh", default=None, help="render this triangle mesh (PLY, or a textured OBJ) along the spiral in place of the model")
-    p.add_argument("--shading", choices=("colour", "normal", "texture"), default=None,
-                   help="with --mesh: vertex colours (the default for a .ply), face normals, or the atlas (implied by a .obj)")
+    p.add_argument("--shading", choices=("colour", "normal", "smooth", "lit", "texture"), default=None,
+                   help="with --mesh: vertex colours (the default for a .ply), face normals, vertex normals as colours (smooth) or as a grey "
+                        "headlight (lit), or the atlas (implied by a .obj)")
     a = p.parse_args(argv)
     if a.no_png and not a.video:
         p.error("--no_png needs --video")

@@ -977,6 +977,73 @@ int b3gs_mesh_resolve_textured_batch(int32_t nviews, const float* cameras, int32
                                      const uint8_t* texture, int32_t cell, int32_t Wt, int32_t Ht, int32_t* triangle_id, float* depth,
                                      float* alpha, float* colour, int32_t* face_pixels, b3gs_stream_t stream);
 
+/* ---- smoothing an extracted mesh: vertex adjacency, Taubin filter, vertex normals, shaded resolve (ABI 18, added entry points;
+ * binocular3dgs_amd/mesh_tools.py, mesh_render.py) --------------------------------------------------
+ * Six entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * Integer work, stable sorts, ordered scans, and fp64 / float32 statements of one correctly rounded operation each that ONE
+ * thread per vertex (or pixel) executes in one fixed order: tests/meshsmooth_ref.py restates every statement in numpy and every
+ * output agrees bit for bit.  The translation unit is compiled with -ffp-contract=off; no floating-point atomic anywhere.
+ * Nothing synchronises or reads the device: every call is capturable in a graph.  The workspace is 256-byte aligned,
+ * b3gs_mesh_adjacency_workspace_bytes(V, F) bytes (0 for bad sizes; about 130 bytes per triangle and 50 per vertex), needs no
+ * initial content, and is what build fills and smooth / vertex_normals read: it stays valid while the faces are unchanged.
+ * V <= 2^31 - 1, 6 F <= 2^31 - 1.
+ *
+ * a. validity  a face with an index outside 0 .. V-1 is bad: counted, and it contributes nothing anywhere.  A vertex with a
+ *              coordinate that is not finite is counted (by build, smooth and vertex_normals alike, each for the vertices it
+ *              is given: word 1 below describes the latest call).  Every kernel still runs to its end; with such vertices the
+ *              positions and normals are unspecified.
+ * b. pairs     every good face (a, b, c) gives the ordered pairs (a,b), (b,a), (b,c), (c,b), (c,a), (a,c); a pair with equal
+ *              ends is dropped.  The pairs are sorted stably by second, then by first, the two orders composed; head flags and
+ *              the ordered scan give the distinct pairs.  The neighbours of vertex i are the seconds of its distinct pairs,
+ *              ascending: CSR, offsets int32 [V + 1] and indices int32 [<= 6 F].
+ * c. edges     a distinct pair with first < second is an undirected edge; m, the length of its run in the sorted list, is the
+ *              number of good faces that contain it (a face listed twice counts twice, and a degenerate face (a, a, b) names
+ *              its one edge twice).  m = 1: boundary, m = 2: interior,
+ *              m > 2: non-manifold.  A vertex is pinned-eligible when it is an end of an edge with m != 2, isolated when its
+ *              neighbour list is empty.
+ * d. incidence each good face gives three (corner, face) slots, a vertex named twice by the face one; sorted stably by vertex:
+ *              the faces of a vertex in face-index order.
+ * e. totals    eight int64 at the START of the workspace: {bad faces, vertices that are not finite, distinct undirected edges,
+ *              boundary edges, non-manifold edges, pinned-eligible vertices, isolated vertices, good faces}.
+ * f. step      with factor k, thread = vertex i with neighbours j_0 < j_1 < .. (deg of them), per axis, fp64 from float32:
+ *                s = 0;  s += (double) x_j  for j ascending;  m = s / (double) deg;  d = m - (double) x_i;  t = k * d
+ *                x'_i = (float)((double) x_i + t)
+ *              An isolated vertex is copied, and with pin_boundary so is a pinned-eligible one.  Jacobi: a step reads one
+ *              buffer and writes the other.  iterations = n: steps 0 .. 2n - 1, the even ones with k = lambda, the odd ones
+ *              with k = mu; mu = 0 skips the odd ones (a Laplacian filter of n steps); n = 0 copies.  0 < lambda <= 1, and mu = 0
+ *              or mu < -lambda (Taubin); n <= 2^20.  out_vertices may be the input.
+ * g. normals   thread = vertex, over its incident faces in face-index order, fp64 from float32, one operation per statement:
+ *                u = p1 - p0, v = p2 - p0;  n = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x);  N += n per component
+ *              l = sqrt((N_x N_x + N_y N_y) + N_z N_z);  normal = (float)(N_a / l) per component, (0, 0, 0) when l is 0 or not
+ *              finite.  Area weights only.
+ * h. shaded    b3gs_mesh_resolve_batch (statement 7 of the rasterizer) with the same cameras, faces and workspace, the same E_k,
+ *              b_k, w_k, z, triangle_id, depth, alpha and face_pixels; normals float32 [V, 3].  The colour of a covered pixel, in
+ *              float32, with n_k the normals of the winner's corners:
+ *                g_a = ((w_0 n_0a + w_1 n_1a) + w_2 n_2a) * z                                     world space, a = x, y, z
+ *                c_r = (rot[3r] g_x + rot[3r+1] g_y) + rot[3r+2] g_z                              camera space
+ *                l = sqrt((c_x c_x + c_y c_y) + c_z c_z) (correctly rounded);  c = c / l per component (0 when l is 0 or not
+ *                finite), negated when the winner has A > 0
+ *                B3GS_MESH_SHADE_SMOOTH  (c + 1) * 0.5 per component
+ *                B3GS_MESH_SHADE_LIT     t = max(-c_z, 0);  v = 0.85 t;  v = v + 0.15: a grey headlight, on the three channels
+ *              Empty pixels take bg.
+ * b3gs_mesh_adjacency_layout: the byte offsets in the workspace of {neighbour offsets int32 [V + 1], neighbour indices int32 [6 F],
+ * incidence ranges (first, one past last) uint32 [V, 2], incident faces int32 [3 F], pinned-eligible mask uint8 [V]}, for callers
+ * that read the lists (the tests do). */
+#define B3GS_MESH_SHADE_SMOOTH 2
+#define B3GS_MESH_SHADE_LIT 3
+size_t b3gs_mesh_adjacency_workspace_bytes(int64_t V, int64_t F);
+int b3gs_mesh_adjacency_layout(int64_t V, int64_t F, size_t* offsets);
+int b3gs_mesh_adjacency_build(int32_t V, int64_t F, const float* vertices, const int32_t* faces, void* workspace,
+                              b3gs_stream_t stream);
+int b3gs_mesh_smooth(int32_t V, int64_t F, const float* vertices, void* workspace, int32_t iterations, double lambda, double mu,
+                     int32_t pin_boundary, float* out_vertices, b3gs_stream_t stream);
+int b3gs_mesh_vertex_normals(int32_t V, int64_t F, const float* vertices, const int32_t* faces, void* workspace, float* normals,
+                             b3gs_stream_t stream);
+int b3gs_mesh_resolve_shaded_batch(int32_t nviews, const float* cameras, int32_t W, int32_t H, int32_t V, int64_t F,
+                                   const float* normals, const int32_t* faces, const void* workspace, const float* bg, int32_t mode,
+                                   int32_t* triangle_id, float* depth, float* alpha, float* colour, int32_t* face_pixels,
+                                   b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
