@@ -136,6 +136,11 @@ class B3gsTsdfView(C.Structure):
                 ("trans", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float)]
 
 
+class B3gsLpipsWeights(C.Structure):
+    _fields_ = [("conv_w", C.c_void_p * 13), ("conv_b", C.c_void_p * 13), ("lin", C.c_void_p * 5), ("shift", C.c_float * 3),
+                ("scale", C.c_float * 3)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -182,7 +187,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_mesh_resolve_textured_batch",
            # added to ABI 18: smoothing an extracted mesh
            "b3gs_mesh_adjacency_workspace_bytes", "b3gs_mesh_adjacency_layout", "b3gs_mesh_adjacency_build", "b3gs_mesh_smooth",
-           "b3gs_mesh_vertex_normals", "b3gs_mesh_resolve_shaded_batch")
+           "b3gs_mesh_vertex_normals", "b3gs_mesh_resolve_shaded_batch",
+           # added to ABI 18: LPIPS (VGG) of held-out views
+           "b3gs_lpips_workspace_bytes", "b3gs_lpips_batch", "b3gs_lpips_features")
 
 _lib = None
 
@@ -378,6 +385,12 @@ def lib():
     L.b3gs_mesh_vertex_normals.restype = C.c_int
     L.b3gs_mesh_resolve_shaded_batch.argtypes = [I32, V, I32, I32, I32, I64, V, V, V, V, I32, V, V, V, V, V, V]
     L.b3gs_mesh_resolve_shaded_batch.restype = C.c_int
+    L.b3gs_lpips_workspace_bytes.argtypes = [I32, I32, I32]
+    L.b3gs_lpips_workspace_bytes.restype = C.c_size_t
+    L.b3gs_lpips_batch.argtypes = [I32, V, V, I32, I32, C.POINTER(B3gsLpipsWeights), I32, V, V, V]
+    L.b3gs_lpips_batch.restype = C.c_int
+    L.b3gs_lpips_features.argtypes = [I32, V, I32, I32, C.POINTER(B3gsLpipsWeights), I32, C.POINTER(C.c_void_p), V, V]
+    L.b3gs_lpips_features.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

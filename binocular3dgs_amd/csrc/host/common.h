@@ -81,5 +81,6 @@ void bind_simplify(pybind11::module_& m);
 void bind_meshraster(pybind11::module_& m);
 void bind_texture(pybind11::module_& m);
 void bind_meshsmooth(pybind11::module_& m);
+void bind_lpips(pybind11::module_& m);
 
 }  // namespace b3

@@ -20,7 +20,13 @@ Two numbers that are easy to confuse:
   * metrics.py's PSNR (mode "png") takes the masked branch of image_utils.psnr: one MSE over every element whose mask is
     exactly 1, of images that went through the 8-bit PNG round trip and the mask composite.  An empty mask gives NaN,
     identical images +inf (as in the reference).
-LPIPS is not reproduced: its VGG weights are a network download.
+LPIPS (VGG) is the third number of metrics.py: with `lpips_weights` (lpips.load_weights of the two weight FILES the reference
+downloads; nothing is fetched here) it is computed on the device from the same composited pair that SSIM takes
+(csrc/lpips.hip).  Without weights the results are what they were.
+
+python -m binocular3dgs_amd.evaluate -m MODEL_PATH [-s SOURCE] [--iteration N] [--mode png|report]
+                                     [--lpips_vgg F --lpips_lin F | --lpips_npz F]
+evaluates the test cameras of the dataset folder and writes results.json / per_view.json under method ours_<iteration>.
 """
 from __future__ import annotations
 
@@ -122,15 +128,19 @@ def _psnr(mse):
         return 20.0 * np.log10(1.0 / np.sqrt(mse))
 
 
-def _device_sums(model, cameras, bg, masks, mode_bits: int, want_ssim: bool, batch: int, capacity=None):
-    """-> (sums [N, 2C+2] float64, ssim [N] or None, H*W per view, C), one read-back at the end."""
+def _device_sums(model, cameras, bg, masks, mode_bits: int, want_ssim: bool, batch: int, capacity=None, lpips_weights=None):
+    """-> (sums [N, 2C+2] float64, ssim [N] or None, H*W per view, lpips [N] or None), one read-back at the end."""
     from . import _C
     parts = []
+    lp = []
     for idx, imgs in _batches(model, cameras, bg, batch, capacity):
         gts = [cameras[i].original_image for i in idx]
         mk = None if masks is None else [masks[i] for i in idx]
         sums, pi, pg = image_metrics(imgs, gts, mk, mode_bits, prepared=want_ssim)
         ss = _C.ssim(pi, pg, 11, False) if want_ssim else None
+        if lpips_weights is not None:        # metrics.py:105 on the pair of metrics.py:95-96
+            from .lpips import lpips
+            lp.append(lpips(pi, pg, lpips_weights))
         parts.append((idx, sums, ss))
     order = [i for idx, _, _ in parts for i in idx]
     sums = torch.cat([s for _, s, _ in parts]).cpu().numpy()
@@ -138,23 +148,25 @@ def _device_sums(model, cameras, bg, masks, mode_bits: int, want_ssim: bool, bat
     inv = np.empty(len(order), dtype=np.int64)
     inv[np.asarray(order, dtype=np.int64)] = np.arange(len(order))
     hw = np.array([float(cameras[i].image_width * cameras[i].image_height) for i in range(len(cameras))])
-    return sums[inv], (None if ssim is None else ssim[inv]), hw
+    return sums[inv], (None if ssim is None else ssim[inv]), hw, (torch.cat(lp).cpu().numpy()[inv] if lp else None)
 
 
 def evaluate_views(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, mode: str = "report",
-                   batch: int = MAX_BATCH) -> dict:
+                   batch: int = MAX_BATCH, lpips_weights=None) -> dict:
     """SSIM / PSNR / L1 of every camera's render against its `original_image`.
 
     mode "report": both images clamped to [0,1]; PSNR = mean of the per-channel PSNRs (train.py:226-261).
     mode "png":    both images through the 8-bit PNG round trip, composited with `masks` (per camera None, [1,H,W] or
                    [3,H,W]; None = LLFF's all-ones mask), PSNR over the elements whose mask is exactly 1 (metrics.py).
     SSIM is ssim() of the composited pair, L1 the mean |difference| of the same pair.
+    `lpips_weights` (lpips.LpipsWeights): every per-view dict also gets "LPIPS" = lpips(net_type='vgg') of that same pair
+    (metrics.py:105) and the result its fp32 mean; SSIM, PSNR and L1 keep their bits.
     -> {"per_view": [{"SSIM", "PSNR", "L1"}, ...], "SSIM", "PSNR", "L1": fp32 means of the per-view values}."""
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}")
     if not cameras:
         return {"per_view": [], "SSIM": math.nan, "PSNR": math.nan, "L1": math.nan}
-    sums, ssim, hw = _device_sums(model, cameras, bg, masks, MODES[mode], True, batch)
+    sums, ssim, hw, lp = _device_sums(model, cameras, bg, masks, MODES[mode], True, batch, lpips_weights=lpips_weights)
     C = (sums.shape[1] - 2) // 2
     l1 = sums[:, :C].sum(1) / (C * hw)
     if mode == "report":
@@ -162,8 +174,11 @@ def evaluate_views(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, mo
     else:
         psnr = _psnr(sums[:, 2 * C] / sums[:, 2 * C + 1])
     per_view = [{"SSIM": float(s), "PSNR": float(p), "L1": float(a)} for s, p, a in zip(ssim, psnr, l1)]
+    if lp is not None:
+        for v, x in zip(per_view, lp):
+            v["LPIPS"] = float(x)
     res = {"per_view": per_view}
-    for key in ("SSIM", "PSNR", "L1"):     # metrics.py:108-110: torch.tensor(values).mean() -- fp32
+    for key in ("SSIM", "PSNR", "L1") + (("LPIPS",) if lp is not None else ()):     # metrics.py:108-110: torch.tensor(values).mean() -- fp32
         res[key] = float(torch.tensor([v[key] for v in per_view]).mean())
     return res
 
@@ -189,7 +204,7 @@ def training_report(model, test_cameras, train_cameras, bg: torch.Tensor, *, bat
         if not cams:
             continue
         if view_metrics is None:
-            sums, _, hw = _device_sums(model, cams, bg, None, CLAMP, False, batch)
+            sums, _, hw, _ = _device_sums(model, cams, bg, None, CLAMP, False, batch)
             C = (sums.shape[1] - 2) // 2
             vals = zip(sums[:, :C].sum(1) / (C * hw), _psnr(sums[:, C:2 * C] / hw[:, None]).mean(1))
         else:
@@ -207,11 +222,12 @@ def training_report(model, test_cameras, train_cameras, bg: torch.Tensor, *, bat
 # ---- results.json / per_view.json (metrics.py:105-122) ----------------------------------------------------------------
 def write_results(model_path: str, method: str, per_view: Sequence[dict], names: Sequence[str]) -> dict:
     """Writes <model_path>/results.json {method: {"SSIM", "PSNR"}} and per_view.json {method: {"SSIM": {name: v}, "PSNR":
-    {name: v}}} in the reference's layout (json.dump, indent=True), without the LPIPS key.  Means are fp32, as
+    {name: v}}} in the reference's layout (json.dump, indent=True); the "LPIPS" key is written in both files, as
+    metrics.py:112-117 does, when EVERY per-view entry carries it, and left out otherwise.  Means are fp32, as
     torch.tensor(values).mean() is there.  Returns the two dicts."""
     if len(per_view) != len(names):
         raise ValueError("one name per view")
-    keys = ("SSIM", "PSNR")
+    keys = ("SSIM", "PSNR") + (("LPIPS",) if per_view and all("LPIPS" in v for v in per_view) else ())
     vals = {k: torch.tensor([float(v[k]) for v in per_view]) for k in keys}
     full = {method: {k: vals[k].mean().item() for k in keys}}
     per = {method: {k: {name: x for x, name in zip(vals[k].tolist(), names)} for k in keys}}
@@ -221,3 +237,70 @@ def write_results(model_path: str, method: str, per_view: Sequence[dict], names:
     with open(os.path.join(model_path, "per_view.json"), "w") as fp:
         json.dump(per, fp, indent=True)
     return {"results": full, "per_view": per}
+
+
+# ---- command line: metrics.py over the test cameras of a trained model ------------------------------------------------
+def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1, mode: str = "png", lpips_weights=None,
+        masks=None) -> dict:
+    """Loads <model_path>/point_cloud/iteration_<it> and the dataset's test cameras (cfg_args gives the defaults, as in
+    spiral.py), evaluates them, prints the means in metrics.py:107-109's format and writes results.json / per_view.json under
+    method ours_<it>.  `masks`: DTU IDR object masks per test camera (the command line does not read them)."""
+    from .gaussian_model import GaussianModel
+    from .scene import Scene
+    from .spiral import max_iteration, read_cfg_args
+    cfg = read_cfg_args(model_path)
+    source_path = source_path or cfg.get("source_path")
+    if not source_path:
+        raise ValueError("no source path: pass -s or keep cfg_args next to the model")
+    it = max_iteration(model_path) if iteration == -1 else iteration
+    model = GaussianModel(int(cfg.get("sh_degree", 1)))
+    model.load_ply(os.path.join(model_path, "point_cloud", "iteration_" + str(it), "point_cloud.ply"))
+    white = bool(cfg.get("white_background", False))
+    scene = Scene.from_dataset(source_path, None, images=cfg.get("images", "images"), eval=True, n_views=int(cfg.get("n_views", 3)),
+                               dataset_name=cfg.get("dataset_name", "LLFF"), suffix=cfg.get("suffix"),
+                               resolution=cfg.get("resolution", -1), white_background=white,
+                               init_points=cfg.get("init_points", "matcher"), shuffle=False)
+    cams = scene.getTestCameras()
+    if not cams:
+        raise ValueError(f"{source_path}: no test cameras")
+    bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
+    res = evaluate_views(model, cams, bg, masks=masks, mode=mode, lpips_weights=lpips_weights)
+    print("  SSIM : {:>12.7f}".format(res["SSIM"]))
+    print("  PSNR : {:>12.7f}".format(res["PSNR"]))
+    if "LPIPS" in res:
+        print("  LPIPS: {:>12.7f}".format(res["LPIPS"]))
+    print("")
+    names = ["{0:05d}.png".format(i) for i in range(len(cams))]      # render.py:34: the file names metrics.py lists
+    write_results(model_path, "ours_{}".format(it), res["per_view"], names)
+    return res
+
+
+def main(argv=None) -> int:
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m binocular3dgs_amd.evaluate", description=__doc__.split("\n")[0])
+    p.add_argument("-m", "--model_path", required=True)
+    p.add_argument("-s", "--source_path", default=None)
+    p.add_argument("--iteration", type=int, default=-1)
+    p.add_argument("--mode", choices=sorted(MODES), default="png")
+    p.add_argument("--lpips_vgg", default=None, help="torchvision's vgg16-397923af.pth (a file; nothing is fetched)")
+    p.add_argument("--lpips_lin", default=None, help="the LPIPS package's weights/v0.1/vgg.pth")
+    p.add_argument("--lpips_npz", default=None, help="the two files converted once by lpips.save_weights")
+    a = p.parse_args(argv)
+    w = None
+    if a.lpips_npz:
+        if a.lpips_vgg or a.lpips_lin:
+            p.error("--lpips_npz replaces --lpips_vgg / --lpips_lin")
+        from .lpips import load_weights
+        w = load_weights(a.lpips_npz)
+    elif a.lpips_vgg or a.lpips_lin:
+        if not (a.lpips_vgg and a.lpips_lin):
+            p.error("--lpips_vgg and --lpips_lin go together")
+        from .lpips import load_weights
+        w = load_weights(a.lpips_vgg, a.lpips_lin)
+    run(a.model_path, a.source_path, a.iteration, a.mode, w)
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

@@ -1044,6 +1044,57 @@ int b3gs_mesh_resolve_shaded_batch(int32_t nviews, const float* cameras, int32_t
                                    int32_t* triangle_id, float* depth, float* alpha, float* colour, int32_t* face_pixels,
                                    b3gs_stream_t stream);
 
+/* ---- LPIPS (VGG16, version 0.1) of held-out views (ABI 18, added entry points; binocular3dgs_amd/lpips.py, evaluate.py,
+ * INTEGRATION.md section 18) --------------------------------------------------------------------------------------------------
+ * Three entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * The third number of the reference's metrics.py:103-117, lpips(render, gt, net_type='vgg'), from weights the caller brings:
+ * nothing is fetched.  Images are the project's planar float32 [n,3,H,W]; every pointer is a device pointer except `weights`
+ * and `feats` themselves, which are host structures of device pointers.  Nothing synchronises or reads the device.
+ *
+ * network   VGG16 `features` up to relu5_3: 3x3 convolutions (stride 1, zero padding 1, bias, ReLU) of widths
+ *             64, 64 | 128, 128 | 256, 256, 256 | 512, 512, 512 | 512, 512, 512
+ *           with a 2x2 stride-2 max-pool in floor mode between the groups (an odd last row or column is dropped) and none
+ *           after the fifth.  Tap l = 0..4 is the output of the last ReLU of group l: C_l = 64, 128, 256, 512, 512 channels of
+ *           H_l x W_l = floor(H / 2^l) x floor(W / 2^l) pixels.
+ * input     x^ = (x - shift_c) / scale_c in float32, an IEEE division; with normalize != 0, x is 2 x - 1 first (two roundings).
+ *           The zero padding of the first convolution is zero AFTER this step.
+ * conv      implicit GEMM on v_mfma_f32_32x32x2_f32: float32 operands and accumulation.  Per output and per chunk of four input
+ *           channels (the first convolution: its three) one k-ordered fmaf chain from 0, k = 9 c + 3 ky + kx ascending (c the
+ *           input channel, (ky, kx) the tap at offset (ky - 1, kx - 1)); the chunk sums are added in chunk order from 0, then
+ *           the bias, then max(., 0).
+ * weights   conv_w[i]: convolution i's [Cout, Cin, 3, 3] weights repacked as [K', Cout] with row k = 9 c + 3 ky + kx, where
+ *           K' = 9 Cin, but 28 for the first convolution (Cin = 3): its row 27 is zero.  conv_b[i]: [Cout].  lin[l]: [C_l],
+ *           the LPIPS package's lin<l>.model.1.weight.  shift / scale: the six input constants (-.030, -.088, -.188 and
+ *           .458, .448, .450 in the reference).
+ * tap       per pixel of a tapped layer, in fp64 from the float32 features f (image x of the pair) and g (image y):
+ *             nx = sqrt(sum_c f_c^2) + 1e-10, ny likewise;  d_c = f_c / nx - g_c / ny;  t = sum_c lin_c d_c^2   (c ascending)
+ *           summed over the layer's pixels in fp64 -- per-workgroup partials in one fixed tree, folded in index order, no
+ *           floating-point atomic -- and divided by H_l W_l: out[pair, l].  LPIPS of a pair is the sum of its five terms.
+ *           A pair's terms have the same bits alone and at any position of a batch; identical images give exactly 0.
+ * limits    1 <= npairs (nimages) <= B3GS_LPIPS_MAX_PAIRS per call; H, W >= B3GS_LPIPS_MIN_SIDE (below it the fifth layer is
+ *           empty); H W <= 2^24.  Anything else: B3GS_ERR_ARG with a message, nothing launched.
+ * workspace b3gs_lpips_workspace_bytes(npairs, H, W) bytes (0 for sizes outside the limits), 256-byte aligned, no initial
+ *           content needed: two activation buffers of 2 npairs * 64 * H * W floats, and the tap partials.
+ *           b3gs_lpips_features takes b3gs_lpips_workspace_bytes(nimages, H, W).
+ * b3gs_lpips_batch     out: double [npairs, 5], the per-layer means.
+ * b3gs_lpips_features  feats[l]: float32 [nimages, C_l, H_l, W_l], the five tap feature maps before normalisation. */
+#define B3GS_LPIPS_CONVS 13
+#define B3GS_LPIPS_TAPS 5
+#define B3GS_LPIPS_MAX_PAIRS 8
+#define B3GS_LPIPS_MIN_SIDE 16
+typedef struct B3gsLpipsWeights {
+  const float* conv_w[B3GS_LPIPS_CONVS];
+  const float* conv_b[B3GS_LPIPS_CONVS];
+  const float* lin[B3GS_LPIPS_TAPS];
+  float shift[3];
+  float scale[3];
+} B3gsLpipsWeights;
+size_t b3gs_lpips_workspace_bytes(int32_t npairs, int32_t H, int32_t W);
+int b3gs_lpips_batch(int32_t npairs, const float* x, const float* y, int32_t H, int32_t W, const B3gsLpipsWeights* weights,
+                     int32_t normalize, double* out, void* workspace, b3gs_stream_t stream);
+int b3gs_lpips_features(int32_t nimages, const float* x, int32_t H, int32_t W, const B3gsLpipsWeights* weights, int32_t normalize,
+                        float* const* feats, void* workspace, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
