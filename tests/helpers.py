@@ -213,3 +213,247 @@ def rel_l2(a, b):
     a = np.asarray(a, dtype=np.float64).ravel()
     b = np.asarray(b, dtype=np.float64).ravel()
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Scenes of the blend edge tests (tests/test_blend_ref_cpu.py, tests/test_gpu_blend_edges.py): flat splats placed in
+# PIXEL units in front of a camera at the origin looking down +z, so that a list length, a saturation point or a footprint
+# edge can be put where the blend kernels change path.  What a scene really holds is decided by the float64 reference
+# (tests/blend_ref.py) on the projected records, and asserted there.
+# ---------------------------------------------------------------------------------------------------------------------
+BLEND_FOVX = math.radians(60.0)
+BLEND_BG = (0.1, 0.2, 0.3)
+STACK_LENGTHS = (1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 513)
+LADDERS = {"ladder_b": (-0.535, -0.165, 13.064, 0.297), "ladder_c": (0.831, -1.665, 13.374, 0.281)}   # x, y, sigma, opacity
+
+
+def splat_scene(W, H, x, y, sig_a, sig_b, theta, opacity, colour, z):
+    """Scene dict (small_scene's keys, activated parameters, sh_degree 0) of flat splats: centre (x, y) in pixels, standard
+    deviations sig_a, sig_b in pixels along / across the direction theta, at view depth z.  (The projection adds its 0.3
+    pixel^2 dilation and, off axis, a little shear.)"""
+    n = len(x)
+    f64 = lambda a: np.broadcast_to(np.asarray(a, np.float64), (n,)).copy()  # noqa: E731
+    x, y, sig_a, sig_b, theta, opacity, z = (f64(a) for a in (x, y, sig_a, sig_b, theta, opacity, z))
+    fovy = synth.fovy_from(BLEND_FOVX, W, H)
+    tx, ty = math.tan(BLEND_FOVX / 2), math.tan(fovy / 2)
+    fx = W / (2 * tx)
+    X = z * tx * ((2 * x + 1) / W - 1)
+    Y = z * ty * ((2 * y + 1) / H - 1)
+    scales = np.stack([sig_a * z / fx, sig_b * z / fx, 1e-4 * z / fx], 1)
+    rot = np.stack([np.cos(theta / 2), np.zeros(n), np.zeros(n), np.sin(theta / 2)], 1)
+    cam = Camera(*look_at_orbit(0.0), BLEND_FOVX, fovy, W, H)
+    shs = (np.asarray(colour, np.float64).reshape(n, 1, 3) - 0.5) / SH_C0
+    t32 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float32)  # noqa: E731
+    return dict(means3D=t32(np.stack([X, Y, z], 1)), opacities=t32(opacity).reshape(n, 1), scales=t32(scales),
+                rotations=t32(rot), shs=t32(shs), viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform,
+                campos=cam.camera_center, bg=torch.tensor(BLEND_BG), W=W, H=H, tanfovx=tx, tanfovy=ty, sh_degree=0)
+
+
+def _stack(rng, L, cx, cy, sigma, opacity, z0):
+    return dict(x=np.full(L, cx), y=np.full(L, cy), sig_a=np.full(L, sigma), sig_b=np.full(L, sigma), theta=np.zeros(L),
+                opacity=np.full(L, opacity), colour=rng.uniform(0.05, 0.95, (L, 3)), z=z0 + 0.004 * np.arange(L))
+
+
+def _cat(*parts):
+    return {k: np.concatenate([np.asarray(p[k], np.float64) for p in parts]) for k in parts[0]}
+
+
+def _cull_field(rng, W, H, n=600):
+    """Small and elongated splats on and around quadrant / tile corners and edges: a quarter barely visible (opacity 1.1/255
+    to 2/255), a fifth opaque and centred on a pixel (alpha clamped at 0.99 there), aspect up to 20:1, all rotations."""
+    kind = rng.uniform(size=n)
+    gxs, gys = np.arange(0, W + 8, 8), np.arange(0, H + 8, 8)
+    x = rng.choice(gxs, n) - 0.5 + rng.normal(0, 2.0, n)
+    y = rng.choice(gys, n) - 0.5 + rng.normal(0, 2.0, n)
+    edge = rng.uniform(size=n) < 0.4          # on an edge between two corners
+    y = np.where(edge & (rng.uniform(size=n) < 0.5), rng.uniform(-2, H + 2, n), y)
+    x = np.where(edge & (rng.uniform(size=n) < 0.5), rng.uniform(-2, W + 2, n), x)
+    long_ = np.exp(rng.uniform(math.log(0.8), math.log(7.0), n))
+    short = long_ / rng.uniform(1.0, 20.0, n)
+    op = rng.uniform(0.02, 0.6, n)
+    op = np.where(kind < 0.25, rng.uniform(1.1 / 255, 2.0 / 255, n), op)
+    # faint ones: wide enough to be live over several pixels
+    long_ = np.where(kind < 0.25, np.maximum(long_, 2.0), long_)
+    opaque = kind > 0.8
+    op = np.where(opaque, 0.9999, op)
+    x = np.where(opaque, np.round(x) + rng.normal(0, 0.05, n), x)
+    y = np.where(opaque, np.round(y) + rng.normal(0, 0.05, n), y)
+    long_ = np.where(opaque, rng.uniform(1.5, 3.0, n), long_)
+    short = np.where(opaque, long_ * rng.uniform(0.6, 1.0, n), short)
+    return dict(x=x, y=y, sig_a=long_, sig_b=short, theta=rng.uniform(0, math.pi, n), opacity=op,
+                colour=rng.uniform(0.05, 0.95, (n, 3)), z=rng.uniform(2.0, 6.0, n))
+
+
+def blend_scene(name, W=None, H=None):
+    """The scenes of the blend edge tests, by name -> scene dict (splat_scene):
+      stack<L>   64 x 16: L identical wide splats (sigma 10, opacity 0.009) on the centre of tile 0: every pixel of the tile
+                 blends all L.  (By the reference's 3-sigma rectangle such a footprint also reaches tiles 1 and 2, which hold
+                 the same list with fewer live pixels; tile 3 stays empty.  Only tile 0 is the designed stack -- n_contrib = L
+                 at every pixel, the backward starts exactly at the list's end; in tiles 1 and 2 n_contrib is mixed.)
+      ladder_b / ladder_c   64 x 16: 300 identical splats (LADDERS: sigma ~13, opacity ~0.29) centred next to the corner of
+                 tile 0: alpha falls off smoothly across tiles 0-2, pixels saturate at list positions ~30-290; the quadrants
+                 of tile 0 finish at ~37, 67, 68 and 118 (tile 0 is done before its second 256-entry chunk).  The centres were
+                 searched so that the two scenes together hold pixels saturating at every position 62..66 and 254..258.
+      cull       the cull field (default 96 x 64; any W, H)
+      wide       64 x 16: stack65 behind one splat of sigma 40 over every tile"""
+    rng = np.random.RandomState(abs(hash_name(name)) % (2 ** 31))
+    if name.startswith("stack"):
+        W, H = 64, 16
+        spec = _stack(rng, int(name[5:]), 7.5, 7.5, 10.0, 0.009, 2.0)
+    elif name in ("ladder_b", "ladder_c"):
+        W, H = 64, 16
+        spec = _stack(rng, 300, *LADDERS[name], 2.0)
+    elif name.startswith("cull"):          # ("cull" + anything: another draw of the field)
+        W, H = W or 96, H or 64
+        spec = _cull_field(rng, W, H)
+    elif name == "wide":
+        W, H = 64, 16
+        wide = dict(x=[31.5], y=[7.5], sig_a=[40.0], sig_b=[40.0], theta=[0.0], opacity=[0.3], colour=[[0.8, 0.3, 0.5]], z=[1.5])
+        spec = _cat(wide, _stack(rng, 65, 7.5, 7.5, 10.0, 0.009, 2.0))
+    else:
+        raise KeyError(name)
+    return splat_scene(W, H, **spec)
+
+
+def hash_name(name):
+    """A seed from a scene name that does not depend on the interpreter's string hashing."""
+    return sum((i + 1) * ord(c) for i, c in enumerate(name)) * 2654435761 % (2 ** 31)
+
+
+def oracle_records(st):
+    """[P, 10] float32 records (x, y, conic xx, xy, yy, opacity, r, g, b, depth) of an oracle.tile_ref State."""
+    return np.concatenate([st.means2D, st.conic_opacity[:, :3], st.conic_opacity[:, 3:4], st.rgb, st.depths[:, None]],
+                          1).astype(np.float32)
+
+
+# Bounds of the blend edge tests: 10 x the largest 99th percentile of float32 blend_ref against float64 blend_ref over
+# BLEND_CASES (tests/test_blend_ref_cpu.py measures and pins them; the figures are in tests/test_gpu_blend_edges.py).
+# images: |x - ref| <= bound (1 + |ref|); final_T: absolute; rows: row_err.  The image measurement asks for 3.3e-5
+# (stack513); the bound stays at the existing contract of 3e-5.
+BLEND_IMG_BOUND, BLEND_T_BOUND, BLEND_ROW_BOUND = 3.0e-5, 2.1e-5, 1.1e-4
+BLEND_IMG_CONTRACT = 3.0e-5
+BLEND_CASES = tuple(("stack%d" % L, None, None) for L in STACK_LENGTHS) + (
+    ("ladder_b", None, None), ("ladder_c", None, None), ("cull", 96, 64), ("cull", 72, 41), ("cull", 75, 33), ("wide", None, None))
+BLEND_STRATA = ("cullable", "corner", "seam", "sat_at_seam", "late", "clamped", "faint")
+# floors of the populations a scene must hold (Gaussians per stratum, after fragility); pairs: (tile, quadrant, Gaussian)
+BLEND_FLOORS = {"cull": dict(cullable=150, corner=100, clamped=50, faint=20, seam=10, sat_at_seam=20),
+                "ladder_b": dict(corner=20, seam=6, sat_at_seam=50, late=3), "ladder_c": dict(corner=20, seam=6, sat_at_seam=50, late=3)}
+BLEND_PAIR_FLOORS = {"cull": dict(cullable=200, corner=100)}
+
+
+def blend_pixel_grads(W, H, seed=3):
+    """Seeded float32 pixel gradients (colour [3,H,W], depth, alpha [H,W]) of the blend edge tests."""
+    rng = np.random.RandomState(seed)
+    hw = W * H
+    return ((rng.normal(size=(3, H, W)) / (3 * hw)).astype(np.float32), (rng.normal(size=(H, W)) / hw).astype(np.float32),
+            (rng.normal(size=(H, W)) / hw).astype(np.float32))
+
+
+def blend_populations(name, st, masks, lost, pr, tight=False):
+    """Assert what the tests rely on in scene `name` (a float64 blend_ref State and its strata); -> figures to print.
+    tight: the lists are those of tight binning -- shorter, so the floors tied to a list POSITION (seam, sat_at_seam) and
+    the ladders' designed finish positions do not apply; the footprint strata do."""
+    from blend_ref import SEAMS
+    key = "cull" if name.startswith("cull") else name
+    pop = {k: (int(masks[k].sum()), int(lost[k].sum())) for k in BLEND_STRATA}
+    for k, (n, gone) in pop.items():
+        assert gone <= 0.1 * n, f"{name}: stratum {k} loses {gone} of {n} members to fragility"
+    for k, floor in BLEND_FLOORS.get(key, {}).items():
+        if tight and k in ("seam", "sat_at_seam"):
+            continue
+        assert pop[k][0] - pop[k][1] >= floor, f"{name}: stratum {k} holds {pop[k]} (floor {floor})"
+    npairs = dict(cullable=int((pr["reach"] & pr["walked"] & (pr["n_alive"] == 0) & ~pr["near"]).sum()),
+                  corner=int(((pr["n_blend"] >= 1) & (pr["n_blend"] <= 3) & (pr["n_solid"] >= 1)).sum()))
+    for k, floor in BLEND_PAIR_FLOORS.get(key, {}).items():
+        assert npairs[k] >= floor, f"{name}: {npairs[k]} {k} pairs (floor {floor})"
+    W, H = st.W, st.H
+    if name.startswith("stack"):
+        L = int(name[5:])
+        assert (st.n_contrib[:16, :16] == L).all() and st.work[0] == L, "every pixel of tile 0 blends the whole stack"
+        assert len(st.ids[3]) == 0, "tile 3 is empty"
+        assert pop["seam"][0] == sum(s < L for s in SEAMS)
+    if name.startswith("ladder") and not tight:
+        fin = {t: sorted(set(pr["finish"][(pr["tile"] == t)].tolist())) for t in range(3)}
+        assert max(fin[0]) - min(fin[0]) > 64, f"a quadrant of tile 0 finishes more than 64 entries before another: {fin[0]}"
+        assert max(fin[0]) < 256 < len(st.ids[0]), "tile 0 finishes before its last chunk"
+        if name == "ladder_b":   # quadrant finish positions of every residue mod 4 (the forward looks every 4th candidate)
+            assert {f % 4 for f in fin[0] + fin[1] + fin[2] if 0 < f < len(st.ids[0])} == {0, 1, 2, 3}, fin
+        # the saturating entry is not blended, final_T is the value before it
+        sat = st.sat_pos >= 0
+        assert sat.any() and (st.n_contrib[sat] <= st.sat_pos[sat]).all() and (st.final_T[sat] >= 1e-4).all()
+    if key == "cull" and (W % 16 or H % 16):
+        t_out = [(t, q) for t, q, f_ in zip(pr["tile"], pr["quad"], pr["finish"]) if f_ == 0 and st.work[t] > 0]
+        assert len(t_out) > 0, "a tile with work holds a quadrant wholly outside the image"
+    if name == "wide":
+        wide = (pr["gid"] == 0) & (pr["n_blend"] > 0)
+        assert wide.sum() == 16, "the wide splat is blended by every quadrant of every tile"
+    return pop, npairs
+
+
+BLEND_BATCH_SIZES = ((80, 48), (72, 41), (33, 17))
+BLEND_BATCH_FLOORS = dict(touched=400, cullable=100, corner=100)
+
+
+def blend_batch_scenes(name="cull_batch7", sizes=BLEND_BATCH_SIZES):
+    """One cull field (built for the first size) seen by cameras of several resolutions: the views of a batched launch."""
+    ds = [blend_scene(name, *sizes[0])]
+    for W, H in sizes[1:]:
+        e = splat_scene(W, H, [0.0], [0.0], 1.0, 1.0, 0.0, 0.5, [[0.5, 0.5, 0.5]], 2.0)
+        d = dict(ds[0])
+        d.update({k: e[k] for k in ("viewmatrix", "projmatrix", "campos", "W", "H", "tanfovx", "tanfovy")})
+        ds.append(d)
+    return ds
+
+
+# The two-segment scene: P = 4096 + 512, 160 x 16 (ten tiles).  Segment 1 of a two-round forward is the nearest 4096 Gaussians
+# of the depth order; most of those sit far outside the image (they take their place in the order and emit no instance), so
+# that the number of segment-1 entries per tile -- len1 -- is chosen per tile: (len1, len2) below, narrow splats (sigma 2.1:
+# the reference's rectangle stays inside the tile) that leave the corners of their tile untouched, i.e. the tile open.  Tile 9
+# holds 30 wide opaque splats of segment 1 that terminate every pixel of it -- no segment 2 may arrive there although ten wide
+# splats of segment 2 lie on it -- and spill into tiles 7 and 8, which stay open.  Tile 6 is empty.
+TWO_SEG_P, TWO_SEG_K1, TWO_SEG_SIZE = 4096 + 512, 4096, (160, 16)
+TWO_SEG_TILES = {0: (64, 20), 1: (70, 30), 2: (128, 10), 3: (100, 70), 4: (0, 12), 5: (256, 40)}
+TWO_SEG_OPAQUE = (30, 10)
+
+
+def two_segment_scene():
+    rng = np.random.RandomState(hash_name("two_segments"))
+    W, H = TWO_SEG_SIZE
+    parts1, parts2 = [], []
+    for t, (n1, n2) in TWO_SEG_TILES.items():
+        for n, parts, z0 in ((n1, parts1, 2.0), (n2, parts2, 4.0)):
+            if n:
+                s = _stack(rng, n, 16 * t + 7.5, 7.5, 2.1, 0.03, z0 + 0.05 * t)
+                s["z"] = z0 + 0.05 * t + 1e-4 * np.arange(n)
+                parts.append(s)
+    for n, parts, z0 in ((TWO_SEG_OPAQUE[0], parts1, 2.9), (TWO_SEG_OPAQUE[1], parts2, 4.9)):
+        s = _stack(rng, n, 16 * 9 + 7.5, 7.5, 12.0, 0.9, z0)
+        s["z"] = z0 + 1e-4 * np.arange(n)
+        parts.append(s)
+    n_on1, n_on2 = sum(len(p["x"]) for p in parts1), sum(len(p["x"]) for p in parts2)
+    for n, parts, z0 in ((TWO_SEG_K1 - n_on1, parts1, 1.0), (TWO_SEG_P - TWO_SEG_K1 - n_on2, parts2, 6.0)):
+        s = _stack(rng, n, -400.0, 7.5, 1.0, 0.5, z0)       # outside the image: a place in the depth order, no instance
+        s["z"] = z0 + 1e-4 * np.arange(n)
+        parts.append(s)
+    return splat_scene(W, H, **_cat(*(parts1 + parts2)))
+
+
+def two_segment_populations(len1, len2, opaque_tile=9):
+    """Assert, from per-tile segment lengths, what the two-segment test relies on."""
+    len1, len2 = np.asarray(len1), np.asarray(len2)
+    both = (len1 > 0) & (len2 > 0)
+    assert (both & (len1 % 64 == 0)).any(), f"no open tile whose len1 sits on a 64-entry word boundary: {len1} {len2}"
+    assert (both & (len1 % 64 != 0)).any(), f"no open tile whose len1 falls strictly inside a word: {len1} {len2}"
+    assert ((len1 == 0) & (len2 > 0)).any(), "no tile that holds segment 2 only"
+    assert len1[opaque_tile] > 0 and len2[opaque_tile] == 0, "the terminated tile must not receive a segment 2"
+    assert (both & (len1 + len2 > 256)).any(), "no list that crosses a staged chunk behind the segment switch"
+
+
+def blend_batch_populations(st, pr, touched):
+    """Floors for a view of the batched launch (the smallest, 33 x 17, is 3 x 2 ragged tiles) -> the figures."""
+    fig = dict(touched=int(touched.sum()),
+               cullable=int((pr["reach"] & pr["walked"] & (pr["n_alive"] == 0) & ~pr["near"]).sum()),
+               corner=int(((pr["n_blend"] >= 1) & (pr["n_blend"] <= 3) & (pr["n_solid"] >= 1)).sum()))
+    for k, floor in BLEND_BATCH_FLOORS.items():
+        assert fig[k] >= floor, f"batch view {st.W}x{st.H}: {k} {fig[k]} (floor {floor})"
+    return fig
