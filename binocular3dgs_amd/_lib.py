@@ -141,6 +141,15 @@ class B3gsLpipsWeights(C.Structure):
                 ("scale", C.c_float * 3)]
 
 
+class B3gsContribView(C.Structure):
+    _fields_ = [("view", C.POINTER(B3gsScene)), ("geometry", C.c_void_p), ("binning", C.c_void_p), ("image", C.c_void_p),
+                ("pixel_mask", C.c_void_p)]
+
+
+class B3gsContribOut(C.Structure):
+    _fields_ = [("weight_q32", C.c_void_p), ("hits", C.c_void_p), ("wmax_bits", C.c_void_p), ("dominant", C.c_void_p)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -189,7 +198,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_mesh_adjacency_workspace_bytes", "b3gs_mesh_adjacency_layout", "b3gs_mesh_adjacency_build", "b3gs_mesh_smooth",
            "b3gs_mesh_vertex_normals", "b3gs_mesh_resolve_shaded_batch",
            # added to ABI 18: LPIPS (VGG) of held-out views
-           "b3gs_lpips_workspace_bytes", "b3gs_lpips_batch", "b3gs_lpips_features")
+           "b3gs_lpips_workspace_bytes", "b3gs_lpips_batch", "b3gs_lpips_features",
+           # added to ABI 18: per-Gaussian render contribution
+           "b3gs_blend_contribution_batch")
 
 _lib = None
 
@@ -391,6 +402,8 @@ def lib():
     L.b3gs_lpips_batch.restype = C.c_int
     L.b3gs_lpips_features.argtypes = [I32, V, I32, I32, C.POINTER(B3gsLpipsWeights), I32, C.POINTER(C.c_void_p), V, V]
     L.b3gs_lpips_features.restype = C.c_int
+    L.b3gs_blend_contribution_batch.argtypes = [I32, C.POINTER(B3gsContribView), C.POINTER(B3gsContribOut), V]
+    L.b3gs_blend_contribution_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

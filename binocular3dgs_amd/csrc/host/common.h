@@ -82,5 +82,6 @@ void bind_meshraster(pybind11::module_& m);
 void bind_texture(pybind11::module_& m);
 void bind_meshsmooth(pybind11::module_& m);
 void bind_lpips(pybind11::module_& m);
+void bind_contrib(pybind11::module_& m);
 
 }  // namespace b3

@@ -54,9 +54,10 @@ def read_cfg_args(model_path: str) -> dict:
 
 
 def max_iteration(model_path: str) -> int:
-    """utils/system_utils.py searchForMaxIteration over <model_path>/point_cloud/iteration_<n>."""
+    """utils/system_utils.py searchForMaxIteration over <model_path>/point_cloud/iteration_<n>; a folder whose suffix is no
+    number (iteration_<n>_pruned of prune.py) is no iteration of the training run and is passed over."""
     names = os.listdir(os.path.join(model_path, "point_cloud"))
-    its = [int(n.split("_")[-1]) for n in names if n.startswith("iteration_")]
+    its = [int(n.split("_")[-1]) for n in names if n.startswith("iteration_") and n.split("_")[-1].isdigit()]
     if not its:
         raise FileNotFoundError(f"no point_cloud/iteration_* under {model_path}")
     return max(its)

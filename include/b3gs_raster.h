@@ -1095,6 +1095,42 @@ int b3gs_lpips_batch(int32_t npairs, const float* x, const float* y, int32_t H, 
 int b3gs_lpips_features(int32_t nimages, const float* x, int32_t H, int32_t W, const B3gsLpipsWeights* weights, int32_t normalize,
                         float* const* feats, void* workspace, b3gs_stream_t stream);
 
+/* ---- per-Gaussian render contribution (added to ABI 18) ------------------------------------------------
+ * A second walk of the tile lists that a finished forward left on the device (b3gs_forward_raw[_batch] with the blend, or
+ * b3gs_blend_forward_batch): per pixel the list the blend backward walks -- segment 1 followed by segment 2 -- over the
+ * positions below that pixel's n_contrib (clamped to the list length), transmittance T restarted from 1.  An entry is
+ * blended exactly where the forward blended it (not power > 0, alpha = min(0.99, opacity exp(power)) >= 1/255, evaluated by
+ * the forward's own device function); the saturation stop is not evaluated again, n_contrib ends the walk in front of the
+ * stopping entry.  Every blended (pixel, entry) has the weight w = alpha * T, T the transmittance in front of the entry; the
+ * alpha image of the forward is the sum of w over a pixel's entries.
+ *
+ * Four arrays of [P], shared by all views of a call and ACCUMULATED INTO (the caller zeroes them):
+ *   weight_q32  sum of rint(w * 2^32) over the counted pixels.  The product is exact in float32; the conversion rounds to
+ *               nearest, ties to even (it only rounds where w < 2^-9); 64-bit integer adds.  weight = weight_q32 / 2^32.
+ *   hits        number of (view, pixel) the Gaussian was blended into
+ *   wmax_bits   float32 bits of the largest w (w >= 0, so unsigned order is float order); unsigned max
+ *   dominant    number of (view, pixel) at which it has the largest w of the pixel; ties go to the first in list order
+ * Nothing but integer adds and max reaches memory: the results do not depend on any order, a view gives the same bits
+ * alone and at any position of a batch, and two calls give the same bits.  The 32-bit counters wrap after 2^32 pixels:
+ * fold and zero them between calls (8 views of 16k x 16k still fit one call).
+ * pixel_mask: [H*W] bytes, nonzero = count the pixel; NULL = every pixel.  Pixels outside W x H never count.
+ * The call reads geometry / binning / image and writes only the four arrays.  All views share P.  1..8 views per call;
+ * arguments are checked before the first HIP call (B3GS_ERR_ARG). */
+typedef struct B3gsContribView {
+  const B3gsScene* view;         /* P, W, H are read */
+  const char* geometry;          /* as left by b3gs_forward_raw[_batch] + the blend forward of this view */
+  const char* binning;
+  const char* image;
+  const uint8_t* pixel_mask;     /* [H*W], nonzero = count this pixel; NULL = every pixel */
+} B3gsContribView;
+typedef struct B3gsContribOut {  /* [P] each, shared by all views of the call, accumulated into; the caller zeroes */
+  uint64_t* weight_q32;          /* sum over counted pixels of rint(w * 2^32), w = alpha * T (T before the blend) */
+  uint32_t* hits;                /* number of (view, pixel) the Gaussian was blended into */
+  uint32_t* wmax_bits;           /* bits of the largest float32 w (w >= 0: unsigned order = float order) */
+  uint32_t* dominant;            /* number of (view, pixel) where it has the largest w; ties: first in list order */
+} B3gsContribOut;
+int b3gs_blend_contribution_batch(int32_t nviews, const B3gsContribView* views, const B3gsContribOut* out, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
