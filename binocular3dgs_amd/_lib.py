@@ -146,6 +146,12 @@ class B3gsContribView(C.Structure):
                 ("pixel_mask", C.c_void_p)]
 
 
+class B3gsPixelMapView(C.Structure):
+    _fields_ = [("view", C.POINTER(B3gsScene)), ("geometry", C.c_void_p), ("binning", C.c_void_p), ("image", C.c_void_p),
+                ("median_depth", C.c_void_p), ("depth_m1", C.c_void_p), ("depth_m2", C.c_void_p), ("dominant", C.c_void_p),
+                ("count", C.c_void_p)]
+
+
 class B3gsContribOut(C.Structure):
     _fields_ = [("weight_q32", C.c_void_p), ("hits", C.c_void_p), ("wmax_bits", C.c_void_p), ("dominant", C.c_void_p)]
 
@@ -200,7 +206,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: LPIPS (VGG) of held-out views
            "b3gs_lpips_workspace_bytes", "b3gs_lpips_batch", "b3gs_lpips_features",
            # added to ABI 18: per-Gaussian render contribution
-           "b3gs_blend_contribution_batch")
+           "b3gs_blend_contribution_batch",
+           # added to ABI 18: per-pixel geometry maps
+           "b3gs_blend_pixel_maps_batch")
 
 _lib = None
 
@@ -404,6 +412,8 @@ def lib():
     L.b3gs_lpips_features.restype = C.c_int
     L.b3gs_blend_contribution_batch.argtypes = [I32, C.POINTER(B3gsContribView), C.POINTER(B3gsContribOut), V]
     L.b3gs_blend_contribution_batch.restype = C.c_int
+    L.b3gs_blend_pixel_maps_batch.argtypes = [I32, C.POINTER(B3gsPixelMapView), V]
+    L.b3gs_blend_pixel_maps_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,6 +1,6 @@
 """python -m binocular3dgs_amd.eval_mesh --mesh MESH.ply --gt CLOUD.ply --spacing S --max_dist D --tau T
                                          [--keep_largest K] [--min_triangles M]
-                                         [-m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--views train|test|all]]
+                                         [-m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--views train|test|all] [--depth mean|median]]
 
 Scores a triangle mesh (the files mesh.write_mesh_ply writes) against a reference point cloud (any PLY whose vertex element
 has x, y, z), on the device: the mesh is optionally cleaned (mesh_tools.clean), sampled at `spacing` (the vertices plus a
@@ -10,7 +10,8 @@ accuracy, completeness, chamfer, and precision, recall and F-score at `tau`.  Pr
 mesh_results.json next to the mesh.
 
 With -m the mesh is also rendered into the model's cameras (extract_mesh's way of finding them) and compared with the model's
-own rendered depth there (mesh_render.depth_agreement): the dict goes into the result as "depth_agreement".
+own rendered depth there (mesh_render.depth_agreement): the dict goes into the result as "depth_agreement".  --depth median
+compares with the model's median depth (pixel_maps.py), the depth extract_mesh --depth median fuses.
 
 This is the measure of the DTU surface benchmark WITHOUT its protocol: the 0.2 mm thinning of both clouds, the observation
 mask and the ground plane belong to the caller, who owns those files (mesh_tools.score_clouds takes the masks).  The numbers
@@ -40,11 +41,12 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("-s", "--source_path", default=None)
     p.add_argument("--iteration", type=int, default=-1)
     p.add_argument("--views", choices=("train", "test", "all"), default="test")
+    p.add_argument("--depth", choices=("mean", "median"), default="mean", help="with -m: the model's depth the mesh is compared with")
     return p
 
 
 def run(mesh_path: str, gt_path: str, spacing: float, max_dist: float, tau: float, keep_largest: int = 0, min_triangles: int = 0,
-        device="cuda", model_path=None, source_path=None, iteration: int = -1, views: str = "test") -> dict:
+        device="cuda", model_path=None, source_path=None, iteration: int = -1, views: str = "test", depth: str = "mean") -> dict:
     from . import mesh, mesh_tools
     from .init_points import read_ply_vertices
     v, c, f = mesh.read_mesh_ply(mesh_path)
@@ -59,13 +61,14 @@ def run(mesh_path: str, gt_path: str, spacing: float, max_dist: float, tau: floa
                    "vertices": int(vertices.shape[0]), "triangles": int(faces.shape[0]), "keep_largest": keep_largest,
                    "min_triangles": min_triangles})
     if model_path is not None:
-        result["depth_agreement"] = model_depth_agreement(model_path, vertices, faces, source_path, iteration, views, device)
+        result["depth_agreement"] = model_depth_agreement(model_path, vertices, faces, source_path, iteration, views, device, depth)
     with open(os.path.join(os.path.dirname(os.path.abspath(mesh_path)), "mesh_results.json"), "w") as fp:
         json.dump(result, fp, indent=2)
     return result
 
 
-def model_depth_agreement(model_path: str, vertices, faces, source_path=None, iteration: int = -1, views: str = "test", device="cuda") -> dict:
+def model_depth_agreement(model_path: str, vertices, faces, source_path=None, iteration: int = -1, views: str = "test", device="cuda",
+                          depth: str = "mean") -> dict:
     """mesh_render.depth_agreement against the trained model of `model_path` in its own cameras"""
     from . import mesh_render
     from .extract_mesh import load_cameras
@@ -80,7 +83,7 @@ def model_depth_agreement(model_path: str, vertices, faces, source_path=None, it
         raise ValueError(f"no {views} cameras")
     white = bool(cfg.get("white_background", False))
     bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device=device)
-    out = mesh_render.depth_agreement(model, vertices, faces, cams, bg)
+    out = mesh_render.depth_agreement(model, vertices, faces, cams, bg, depth=depth)
     out.update({"model": os.path.abspath(model_path), "iteration": it, "camera_set": views})
     return out
 
@@ -88,7 +91,7 @@ def model_depth_agreement(model_path: str, vertices, faces, source_path=None, it
 def main(argv=None) -> int:
     a = parser().parse_args(argv)
     print(json.dumps(run(a.mesh, a.gt, a.spacing, a.max_dist, a.tau, a.keep_largest, a.min_triangles,
-                         model_path=a.model_path, source_path=a.source_path, iteration=a.iteration, views=a.views)))
+                         model_path=a.model_path, source_path=a.source_path, iteration=a.iteration, views=a.views, depth=a.depth)))
     return 0
 
 

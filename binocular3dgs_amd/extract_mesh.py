@@ -1,6 +1,6 @@
 """python -m binocular3dgs_amd.extract_mesh -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--views train|test|all]
                                             [--resolution 256 | --voxel_size S] [--truncation_voxels 4] [--alpha_min 0.5]
-                                            [--min_weight 1] [--bounds x0 y0 z0 x1 y1 z1]
+                                            [--min_weight 1] [--depth mean|median] [--bounds x0 y0 z0 x1 y1 z1]
                                             [--keep_largest 0] [--min_triangles 0] [--cull_unseen [--min_pixels 1]]
                                             [--smooth N [--smooth_lambda 0.5] [--smooth_mu -0.53] [--free_boundary]] [--normals]
                                             [--simplify K | --target_triangles N] [--placement quadric|mean]
@@ -10,7 +10,9 @@
 A triangle mesh of a trained model: the point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply is rendered from
 the chosen cameras, depth, alpha and colour are fused into a TSDF volume and the zero level set is extracted, all on the
 device (mesh.fuse_model).  Writes <model_path>/mesh/iteration_<it>/mesh.ply (binary PLY, coloured vertices) and prints the
-voxel, vertex and triangle counts.  --keep_largest K keeps the K components with the most triangles (ties at the K-th
+voxel, vertex and triangle counts.  --depth median fuses the depth at which a pixel's transmittance crosses one half
+(pixel_maps.py) in place of the alpha-weighted mean, which lies between the surfaces where a semi-transparent Gaussian hangs in
+front of one.  --keep_largest K keeps the K components with the most triangles (ties at the K-th
 all survive), --min_triangles M the components with at least M (mesh_tools.clean); with both at 0 the step is not run.
 --cull_unseen renders the mesh into the cameras of --views (mesh_render.cull_unseen) and drops the triangles that win fewer
 than --min_pixels pixels over all of them, e.g. blobs inside or behind the observed surface; it runs after the cleaning step
@@ -61,6 +63,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--truncation_voxels", type=float, default=4.0)
     p.add_argument("--alpha_min", type=float, default=0.5)
     p.add_argument("--min_weight", type=float, default=1.0)
+    p.add_argument("--depth", choices=("mean", "median"), default="mean",
+                   help="the depth of a pixel that is fused: the alpha-weighted mean, or the depth at which the transmittance crosses 1/2")
     p.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
     p.add_argument("--keep_largest", type=int, default=0, help="keep the K largest connected components (0: all)")
     p.add_argument("--min_triangles", type=int, default=0, help="drop the components with fewer triangles (0: none)")
@@ -141,7 +145,7 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
         keep_largest: int = 0, min_triangles: int = 0, simplify=None, target_triangles=None, placement: str = "quadric",
         cull_unseen: bool = False, min_pixels: int = 1, texture: bool = False, texel_cell=None, atlas_side=None,
         texture_from: str = "render", texture_slack=None, two_sided: bool = False, smooth=None, smooth_lambda: float = 0.5,
-        smooth_mu: float = -0.53, free_boundary: bool = False, normals: bool = False) -> str:
+        smooth_mu: float = -0.53, free_boundary: bool = False, normals: bool = False, depth: str = "mean") -> str:
     from . import mesh
     from .gaussian_model import GaussianModel
     from .spiral import max_iteration, read_cfg_args
@@ -157,7 +161,7 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
     t0 = time.perf_counter()
     vertices, colours, faces, vol = mesh.fuse_model(
         model, cams, bg, resolution=resolution, voxel_size=voxel_size, bounds=None if bounds is None else (bounds[:3], bounds[3:]),
-        truncation_voxels=truncation_voxels, alpha_min=alpha_min, min_weight=min_weight, return_volume=True)
+        truncation_voxels=truncation_voxels, alpha_min=alpha_min, min_weight=min_weight, return_volume=True, depth=depth)
     if keep_largest or min_triangles:
         from . import mesh_tools
         vertices, colours, faces, st = mesh_tools.clean(vertices, colours, faces, keep_largest, min_triangles, return_stats=True)
@@ -249,7 +253,7 @@ def main(argv=None) -> int:
         p.error("--texture_slack is at least 0 and finite")
     run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
         a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement, a.cull_unseen, a.min_pixels,
-        a.texture, a.texel_cell, a.atlas_side, a.texture_from, a.texture_slack, a.two_sided, a.smooth, lam, mu, a.free_boundary, a.normals)
+        a.texture, a.texel_cell, a.atlas_side, a.texture_from, a.texture_slack, a.two_sided, a.smooth, lam, mu, a.free_boundary, a.normals, a.depth)
     return 0
 
 

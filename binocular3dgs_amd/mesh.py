@@ -25,6 +25,7 @@ import torch
 
 MAX_VIEWS = 8          # views per integrate launch (B3GS_MAX_TSDF_VIEWS)
 MAX_DIM = 1024         # voxels per axis (B3GS_MAX_TSDF_DIM)
+DEPTHS = ("mean", "median")   # the depth of a pixel that fuse_model fuses
 NEAR = 0.2             # the renderer's near plane (B3GS_NEAR): a voxel nearer to a camera than this is not seen by it
 
 
@@ -117,12 +118,19 @@ def scene_bounds(model, quantile: float = 0.01, pad: float = 0.0):
 
 def fuse_model(model, cameras: Sequence, bg: torch.Tensor, *, resolution: Optional[int] = None, voxel_size: Optional[float] = None,
                bounds=None, truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, quantile: float = 0.01,
-               batch: int = MAX_VIEWS, return_volume: bool = False):
+               batch: int = MAX_VIEWS, return_volume: bool = False, depth: str = "mean"):
     """Renders `cameras` and fuses depth, alpha and colour into a volume, batch by batch out of the renderer's slot buffers
     (no clones, no host copies), then extracts the mesh.  At most one of resolution (voxels along the longest axis of the
     bounds; default 256) and voxel_size; bounds = (min [3], max [3]), default scene_bounds(), which is then widened by the
-    truncation on every side (2 x truncation_voxels more voxels per axis)."""
+    truncation on every side (2 x truncation_voxels more voxels per axis).
+    depth: which depth of a pixel is fused.  "mean" (the default): the renderer's alpha-weighted mean, rendered_depth /
+    rendered_alpha -- between the surfaces where a semi-transparent Gaussian hangs in front of one.  "median": the depth at
+    which the transmittance crosses one half (pixel_maps.py), always a depth at which a Gaussian sits.  The integration
+    kernel divides its depth input by alpha, so it is handed median_depth * alpha: what it fuses is the median to one float32
+    rounding (x * a / a is within one unit in the last place of x)."""
     from .evaluate import _batches
+    if depth not in DEPTHS:
+        raise ValueError(f"fuse_model: depth is one of {DEPTHS}")
     if resolution is not None and voxel_size is not None:
         raise ValueError("fuse_model: resolution or voxel_size, not both")
     if bounds is None:
@@ -139,9 +147,15 @@ def fuse_model(model, cameras: Sequence, bg: torch.Tensor, *, resolution: Option
         lo, hi = [v - truncation for v in lo], [v + truncation for v in hi]
     vol = TsdfVolume(lo, hi, voxel_size, truncation, device=model.get_xyz.device)
     table = camera_table(cameras)
-    for idx, outs in _batches(model, cameras, bg, batch, full=True):
-        vol.integrate(table[idx], [o["rendered_depth"] for o in outs], [o["rendered_alpha"] for o in outs],
-                      [o["render"] for o in outs], alpha_min=alpha_min)
+    if depth == "median":
+        from .pixel_maps import plane_batches
+        for idx, outs, raws in plane_batches(model, cameras, bg, ("median_depth",), batch=batch):
+            vol.integrate(table[idx], [r["median_depth"] * o["rendered_alpha"].reshape(r["median_depth"].shape) for o, r in zip(outs, raws)],
+                          [o["rendered_alpha"] for o in outs], [o["render"] for o in outs], alpha_min=alpha_min)
+    else:
+        for idx, outs in _batches(model, cameras, bg, batch, full=True):
+            vol.integrate(table[idx], [o["rendered_depth"] for o in outs], [o["rendered_alpha"] for o in outs],
+                          [o["render"] for o in outs], alpha_min=alpha_min)
     mesh = vol.extract(min_weight)
     return mesh + (vol,) if return_volume else mesh
 

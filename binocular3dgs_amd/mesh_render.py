@@ -224,14 +224,19 @@ def cull_unseen(vertices: torch.Tensor, colours: torch.Tensor, faces: torch.Tens
     return mesh_tools.clean(vertices, colours, faces[counts >= int(min_pixels)].contiguous(), 0, 0)
 
 
-def depth_agreement(model, vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequence, bg: torch.Tensor, alpha_min: float = 0.5) -> dict:
+def depth_agreement(model, vertices: torch.Tensor, faces: torch.Tensor, cameras: Sequence, bg: torch.Tensor, alpha_min: float = 0.5,
+                    depth: str = "mean") -> dict:
     """How far the mesh is from the model's own rendered depth in `cameras`: the model is rendered through evaluation's batched
     renderer, the mesh into the same cameras.  With d = |z_mesh - depth / alpha| (fp64) over the pixels where the model's
     alpha >= alpha_min and the mesh covers: mean and median of d (the median is the element of rank (n - 1) // 2),
     model_missed = the share of the model's pixels (alpha >= alpha_min) the mesh does not cover, mesh_uncovered = the share of
-    the mesh's pixels where the model's alpha is below alpha_min.  Sums on the device, one host read at the end."""
+    the mesh's pixels where the model's alpha is below alpha_min.  Sums on the device, one host read at the end.
+    depth="median" compares with the model's median depth (pixel_maps.py; the choice of mesh.fuse_model) in place of
+    depth / alpha: d = |z_mesh - median_depth|."""
     from .evaluate import _batches
-    from .mesh import camera_table
+    from .mesh import DEPTHS, camera_table
+    if depth not in DEPTHS:
+        raise ValueError(f"depth_agreement: depth is one of {DEPTHS}")
     _check_mesh(vertices, None, faces, "depth_agreement")
     cameras = list(cameras)
     table = camera_table(cameras)
@@ -239,15 +244,23 @@ def depth_agreement(model, vertices: torch.Tensor, faces: torch.Tensor, cameras:
     sums = torch.zeros(4, dtype=torch.float64, device=dev)          # sum d, both, model, mesh
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     diffs = []
-    for idx, outs in _batches(model, cameras, bg, MAX_VIEWS, full=True):
+    if depth == "median":
+        from .pixel_maps import plane_batches
+        source = plane_batches(model, cameras, bg, ("median_depth",), batch=MAX_VIEWS)
+    else:
+        source = ((idx, outs, None) for idx, outs in _batches(model, cameras, bg, MAX_VIEWS, full=True))
+    for idx, outs, raws in source:
         W, H = int(cameras[idx[0]].image_width), int(cameras[idx[0]].image_height)
         _, z, cover, _, counts = raster_views(vertices, None, faces, table[idx], W, H, shading="normal")
         bad = counts[MAX_VIEWS:]
-        depth = torch.stack([o["rendered_depth"].reshape(1, H, W) for o in outs]).double()
         alpha = torch.stack([o["rendered_alpha"].reshape(1, H, W) for o in outs])
+        if raws is None:
+            zmodel = torch.stack([o["rendered_depth"].reshape(1, H, W) for o in outs]).double() / alpha.double()
+        else:
+            zmodel = torch.stack([r["median_depth"].reshape(1, H, W) for r in raws]).double()
         m_model, m_mesh = alpha >= alpha_min, cover > 0
         both = m_model & m_mesh
-        d = torch.where(both, (z.double() - depth / alpha.double()).abs(), torch.full_like(depth, float("inf")))
+        d = torch.where(both, (z.double() - zmodel).abs(), torch.full_like(zmodel, float("inf")))
         sums += torch.stack([torch.where(both, d, torch.zeros_like(d)).sum(), both.sum().double(), m_model.sum().double(), m_mesh.sum().double()])
         diffs.append(d.reshape(-1))
     if not diffs:
@@ -257,7 +270,10 @@ def depth_agreement(model, vertices: torch.Tensor, faces: torch.Tensor, cameras:
     total, both, nmodel, nmesh, median, nbad = torch.cat([sums, ordered[rank], bad.double()]).tolist()     # the one host read
     if nbad:
         raise ValueError(f"depth_agreement: {int(nbad)} triangles name a vertex outside 0 .. {vertices.shape[0] - 1}")
-    return {"mean": total / both if both else float("nan"), "median": median if both else float("nan"),
-            "model_missed": (nmodel - both) / nmodel if nmodel else float("nan"),
-            "mesh_uncovered": (nmesh - both) / nmesh if nmesh else float("nan"),
-            "pixels": int(both), "model_pixels": int(nmodel), "mesh_pixels": int(nmesh), "views": len(cameras), "alpha_min": float(alpha_min)}
+    out = {"mean": total / both if both else float("nan"), "median": median if both else float("nan"),
+           "model_missed": (nmodel - both) / nmodel if nmodel else float("nan"),
+           "mesh_uncovered": (nmesh - both) / nmesh if nmesh else float("nan"),
+           "pixels": int(both), "model_pixels": int(nmodel), "mesh_pixels": int(nmesh), "views": len(cameras), "alpha_min": float(alpha_min)}
+    if depth != "mean":          # (the default's dict stays as it was)
+        out["model_depth"] = depth
+    return out

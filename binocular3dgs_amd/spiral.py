@@ -1,5 +1,6 @@
 """python -m binocular3dgs_amd.spiral -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--resolution R] [--white_background]
                                       [--video] [--no_png] [--fps 25] [--quality 90] [--mesh MESH.ply|MESH.obj [--shading colour|normal|smooth|lit|texture]]
+                                      [--maps median,std,id]
 
 The reference's spiral.py: the trained point cloud <model_path>/point_cloud/iteration_<it>/point_cloud.ply, rendered along the
 180-frame spiral of <source_path>/poses_bounds.npy (DTU when the source path contains 'scan'), written as %05d.png,
@@ -16,6 +17,12 @@ extract_mesh --texture writes (with its .mtl and .png); it is rendered through i
 --shading texture is implied by the extension, and is an error for a .ply.  --shading smooth and lit shade a .ply from its
 vertex normals (mesh_render.batches_shaded: the interpolated normal as a colour, or a grey headlight); the normals are those of
 the file (extract_mesh --normals) and are computed on load (mesh_tools.vertex_normals) when it has none.
+
+--maps also writes pictures of the per-pixel geometry maps (pixel_maps.py) of every frame into the same folder: median_%05d.png
+and cmedian_%05d.png (the depth at which the transmittance crosses one half, gray and turbo, encoded as depth_ and cdepth_
+are), std_%05d.png and cstd_%05d.png (the spread of the depth along the ray), id_%05d.png (the Gaussian with the largest
+weight, hashed to a colour); with --video also out_median_<scene>.avi, out_cmedian_, out_std_, out_cstd_, out_id_.  Not with
+--mesh.
 
 Defaults for source_path, sh_degree, resolution and white_background come from <model_path>/cfg_args when it exists (the
 Namespace(...) line train.py writes, read with `ast`: literals only, nothing is executed); the command line wins.
@@ -65,9 +72,11 @@ def max_iteration(model_path: str) -> int:
 
 def run(model_path: str, source_path: str = None, iteration: int = -1, resolution=None, white_background=None,
         sh_degree=None, n_frames: int = 180, video: bool = False, png: bool = True, fps: float = 25.0, quality: int = 90,
-        mesh_path: str = None, shading: str = None) -> str:
+        mesh_path: str = None, shading: str = None, maps=None) -> str:
     from . import camera_path, frames
     from .gaussian_model import GaussianModel
+    if mesh_path is not None and maps:
+        raise ValueError("--maps are maps of the model: not with --mesh")
     if mesh_path is not None:
         return _run_mesh(model_path, source_path, resolution, white_background, n_frames, video, png, fps, quality, mesh_path, shading)
     cfg = read_cfg_args(model_path)
@@ -93,14 +102,27 @@ def run(model_path: str, source_path: str = None, iteration: int = -1, resolutio
         print(f"video (Motion-JPEG AVI, {fps:g} fps, quality {quality}):")
         for path in res["video"]:
             print(f"  {path}")
+        if maps:
+            _run_maps(model, cams, bg, out_dir, maps, (model_path, scene), png, fps, quality)
         return out_dir
     frames.render_path(model, cams, bg, out_dir)
     dt = time.perf_counter() - t0
     print(f"{len(cams)} frames ({cams[0].image_width}x{cams[0].image_height}) -> {out_dir} in {dt:.2f} s")
+    if maps:
+        _run_maps(model, cams, bg, out_dir, maps, None, True, fps, quality)
     print("video (not encoded here):")
     for pat, out in (("%05d.png", "out_{}.mp4"), ("depth_%05d.png", "out_depth_{}.mp4"), ("cdepth_%05d.png", "out_cdepth_{}.mp4")):
         print(f"  ffmpeg -i {os.path.join(out_dir, pat)} -q 2 {os.path.join(model_path, out.format(scene))} -y")
     return out_dir
+
+
+def _run_maps(model, cams, bg, out_dir, maps, video, png, fps, quality):
+    from . import pixel_maps
+    t0 = time.perf_counter()
+    res = pixel_maps.render_map_frames(model, cams, bg, out_dir, maps, video=video, png=png, fps=fps, quality=quality)
+    print(f"maps ({', '.join(maps)}): {len(res['png'])} PNG files -> {out_dir if png else 'no PNG files'} in {time.perf_counter() - t0:.2f} s")
+    for path in res["video"]:
+        print(f"  {path}")
 
 
 def _run_mesh(model_path, source_path, resolution, white_background, n_frames, video, png, fps, quality, mesh_path, shading) -> str:
@@ -165,11 +187,20 @@ def main(argv=None) -> int:
     p.add_argument("--shading", choices=("colour", "normal", "smooth", "lit", "texture"), default=None,
                    help="with --mesh: vertex colours (the default for a .ply), face normals, vertex normals as colours (smooth) or as a grey "
                         "headlight (lit), or the atlas (implied by a .obj)")
+    p.add_argument("--maps", default=None, metavar="median,std,id",
+                   help="also write pictures of the per-pixel geometry maps: median depth, depth spread, dominant Gaussian")
     a = p.parse_args(argv)
     if a.no_png and not a.video:
         p.error("--no_png needs --video")
+    maps = None
+    if a.maps is not None:
+        maps = tuple(m for m in a.maps.split(",") if m)
+        if not maps or any(m not in ("median", "std", "id") for m in maps):
+            p.error("--maps is a comma-separated list out of median, std, id")
+        if a.mesh is not None:
+            p.error("--maps are maps of the model: not with --mesh")
     run(a.model_path, a.source_path, a.iteration, a.resolution, a.white_background, a.sh_degree, a.frames,
-        video=a.video, png=not a.no_png, fps=a.fps, quality=a.quality, mesh_path=a.mesh, shading=a.shading)
+        video=a.video, png=not a.no_png, fps=a.fps, quality=a.quality, mesh_path=a.mesh, shading=a.shading, maps=maps)
     return 0
 
 

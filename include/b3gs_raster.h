@@ -1131,6 +1131,37 @@ typedef struct B3gsContribOut {  /* [P] each, shared by all views of the call, a
 } B3gsContribOut;
 int b3gs_blend_contribution_batch(int32_t nviews, const B3gsContribView* views, const B3gsContribOut* out, b3gs_stream_t stream);
 
+/* ---- per-pixel geometry maps (added to ABI 18) ----------------------------------------------------------
+ * The same second walk of a finished forward's tile lists (above: positions below the pixel's n_contrib, T restarted from 1,
+ * an entry blended exactly where the forward blended it, w = alpha * T with T the transmittance in front of the entry),
+ * reduced per PIXEL.  With d the camera-space depth of an entry's render record, five planes of [H*W] words per view:
+ *
+ *   median_depth  float32  d of the last blended entry whose T BEFORE the blend was > 0.5: the entry at which T crosses one
+ *                          half, or the last blended entry when T never gets there (a pixel of alpha < 0.5); 0 when nothing
+ *                          was blended.  A copy of the record's float, no arithmetic.
+ *   depth_m1      float32  sum of w d   in list order, acc = fmaf(d, w, acc): the forward's statement of its depth image
+ *   depth_m2      float32  sum of w d d in list order, acc = fmaf(w * d, d, acc)
+ *   dominant      int32    Gaussian index of the largest w; ties: the first in list order; -1 when nothing was blended
+ *   count         int32    number of blended entries
+ *
+ * Any plane pointer may be NULL: that plane is not written.  Every pixel inside W x H writes every other plane, so the planes
+ * need no initial content.  The entry that saturates a pixel (T (1 - alpha) < 1e-4) stops it WITHOUT being blended and is in
+ * none of the planes.  No atomics and no reduction across pixels: a view's planes are the same bits whatever else the call
+ * holds.  The call reads geometry / binning / image and writes only the planes.  All views share P (P == 0: nothing is
+ * done), sizes may differ.  1..8 views per call; arguments are checked before the first HIP call (B3GS_ERR_ARG). */
+typedef struct B3gsPixelMapView {
+  const B3gsScene* view;         /* P, W, H are read */
+  const char* geometry;          /* as left by b3gs_forward_raw[_batch] + the blend forward of this view */
+  const char* binning;
+  const char* image;
+  float* median_depth;           /* [H*W] each; NULL = not wanted */
+  float* depth_m1;
+  float* depth_m2;
+  int32_t* dominant;
+  int32_t* count;
+} B3gsPixelMapView;
+int b3gs_blend_pixel_maps_batch(int32_t nviews, const B3gsPixelMapView* views, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
