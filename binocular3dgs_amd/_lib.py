@@ -208,7 +208,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: per-Gaussian render contribution
            "b3gs_blend_contribution_batch",
            # added to ABI 18: per-pixel geometry maps
-           "b3gs_blend_pixel_maps_batch")
+           "b3gs_blend_pixel_maps_batch",
+           # added to ABI 18: weighted k-means codebooks
+           "b3gs_kmeans_workspace_bytes", "b3gs_kmeans_assign", "b3gs_kmeans")
 
 _lib = None
 
@@ -414,6 +416,12 @@ def lib():
     L.b3gs_blend_contribution_batch.restype = C.c_int
     L.b3gs_blend_pixel_maps_batch.argtypes = [I32, C.POINTER(B3gsPixelMapView), V]
     L.b3gs_blend_pixel_maps_batch.restype = C.c_int
+    L.b3gs_kmeans_workspace_bytes.argtypes = [I32, I32, I32]
+    L.b3gs_kmeans_workspace_bytes.restype = C.c_size_t
+    L.b3gs_kmeans_assign.argtypes = [I32, I32, I32, V, V, V, V, V]
+    L.b3gs_kmeans_assign.restype = C.c_int
+    L.b3gs_kmeans.argtypes = [I32, I32, I32, I32, V, V, V, V, V, V, V, V]
+    L.b3gs_kmeans.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

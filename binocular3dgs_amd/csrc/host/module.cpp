@@ -62,4 +62,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_lpips(m);
   b3::bind_contrib(m);
   b3::bind_pixelmaps(m);
+  b3::bind_kmeans(m);
 }

@@ -1162,6 +1162,29 @@ typedef struct B3gsPixelMapView {
 } B3gsPixelMapView;
 int b3gs_blend_pixel_maps_batch(int32_t nviews, const B3gsPixelMapView* views, b3gs_stream_t stream);
 
+/* ---- weighted k-means codebooks (added to ABI 18; binocular3dgs_amd/compress.py, csrc/kmeans.hip) ---------------
+ * Lloyd's algorithm over N rows x [N,D] (float32) with K codes [K,D] and optional row weights w [N] (float32, not negative;
+ * NULL = 1), entirely on the stream: no host read.  1 <= D <= 64, 1 <= K <= 65536, N >= 0 (N == 0: returns B3GS_OK and does
+ * nothing).  NaN and Inf inputs are undefined.
+ *
+ * Assignment:  h_k = float32(0.5 sum_d c_kd^2), summed in fp64 with d ascending; the score of (n, k) is the float32 chain
+ *   a_0 = -h_k, a_{d+1} = fmaf(x_nd, c_kd, a_d), d = 0 .. D-1 (the exact-f32 MFMA); codes[n] = the smallest k whose a_D is
+ *   largest, i.e. the nearest code up to the rounding of that chain.
+ * Update:  c_k = float32(sum w_n x_n / sum w_n) over the rows with code k; sums in fp64 in a fixed order: the members of a
+ *   code in row order, cut into chunks of 256 members, each chunk summed from 0 in member order, the chunk sums added from 0
+ *   in chunk order.  No floating-point atomic.  A code with no member or with sum w == 0 keeps its centroid.
+ * b3gs_kmeans runs assignment 0, then `iters` times (update, assignment): the returned codes belong to the returned codebook.
+ *   codebook  in: the initial codes, out: the final ones        counts [K]: members of the final assignment
+ *   distortion [iters + 1]: sum_n w_n |x_n - c_code(n)|^2 of assignment i, fp64 throughout, folded in a fixed order
+ *   (csrc/kmeans.hip states it; tests/kmeans_ref.py reproduces it).
+ * workspace: b3gs_kmeans_workspace_bytes(N, D, K) bytes (0 for sizes outside the limits), 256-byte aligned, no initial content;
+ *   both calls take the same size.  Arguments are checked before the first HIP call (B3GS_ERR_ARG). */
+size_t b3gs_kmeans_workspace_bytes(int32_t N, int32_t D, int32_t K);
+int b3gs_kmeans_assign(int32_t N, int32_t D, int32_t K, const float* x, const float* codebook, int32_t* codes, void* workspace,
+                       b3gs_stream_t stream);
+int b3gs_kmeans(int32_t N, int32_t D, int32_t K, int32_t iters, const float* x, const float* weights, float* codebook,
+                int32_t* codes, int32_t* counts, double* distortion, void* workspace, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
