@@ -10,7 +10,9 @@
 //      coalesced writes regardless of how many tiles one Gaussian covers),
 //   3. stable LSD radix sort of the N instances by tile id only (ceil(log2(tiles)/8) passes,
 //      2 at 800x600 and 1600x1600) -- stability keeps the depth/index order inside each tile.
-// Resulting point_list is bit-identical to the 64-bit sort (tests/test_gpu_parity.py).
+// Resulting point_list is bit-identical to the 64-bit sort (tests/test_gpu_parity.py; at the radix / scan tile seams, with
+// tied depths, batched, shared and adopted orders, tight rects, capacity and two rounds: tests/test_gpu_binning_edges.py
+// against tests/binning_ref.py).
 //
 // Batching: one view's pass is ~250 workgroups of 4 waves on a 256-CU part (one wave per SIMD: pure
 // latency).  The training iteration renders 6 views of the same Gaussians, so every launch here takes

@@ -416,7 +416,8 @@ TWO_SEG_TILES = {0: (64, 20), 1: (70, 30), 2: (128, 10), 3: (100, 70), 4: (0, 12
 TWO_SEG_OPAQUE = (30, 10)
 
 
-def two_segment_scene():
+def two_segment_scene(P=TWO_SEG_P, K1=TWO_SEG_K1):
+    """(P, K1) other than the defaults: the same tiles with more filler, so that segment 1 is the nearest K1 of P Gaussians"""
     rng = np.random.RandomState(hash_name("two_segments"))
     W, H = TWO_SEG_SIZE
     parts1, parts2 = [], []
@@ -431,7 +432,7 @@ def two_segment_scene():
         s["z"] = z0 + 1e-4 * np.arange(n)
         parts.append(s)
     n_on1, n_on2 = sum(len(p["x"]) for p in parts1), sum(len(p["x"]) for p in parts2)
-    for n, parts, z0 in ((TWO_SEG_K1 - n_on1, parts1, 1.0), (TWO_SEG_P - TWO_SEG_K1 - n_on2, parts2, 6.0)):
+    for n, parts, z0 in ((K1 - n_on1, parts1, 1.0), (P - K1 - n_on2, parts2, 6.0)):
         s = _stack(rng, n, -400.0, 7.5, 1.0, 0.5, z0)       # outside the image: a place in the depth order, no instance
         s["z"] = z0 + 1e-4 * np.arange(n)
         parts.append(s)
@@ -457,3 +458,125 @@ def blend_batch_populations(st, pr, touched):
     for k, floor in BLEND_BATCH_FLOORS.items():
         assert fig[k] >= floor, f"batch view {st.W}x{st.H}: {k} {fig[k]} (floor {floor})"
     return fig
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Scenes of the binning edge tests (tests/test_gpu_binning_edges.py, reference: tests/binning_ref.py): splat_scene under the
+# identity view matrix, so that view z IS the stored z and a depth key can be planted as a bit pattern.  A "one-tile" splat
+# (sigma 0.5 -> radius 3) sits on a tile centre, a "two-tile" one on the edge between two tiles of a row.  What a scene really
+# holds -- N, V, ties, keys, tiles -- is asserted from the device state by the test (the list at the end of this section records what each must hold).
+# ---------------------------------------------------------------------------------------------------------------------
+KEY27_BASE, KEY27_SPAN = 0x3E4CCCCD, 1 << 27          # float bits of the near plane 0.2f; span of the three-pass depth sort
+BIN_SEAM_P = (1, 63, 64, 65, 2047, 2048, 2049, 4095, 4096, 4097, 8193, 16384, 16385, 32769)
+BIN_N_TARGETS = (4095, 4096, 4097, 16384, 16385, 32769)
+BIN_TILE_IMAGES = {"tiles256": (256, 256, 256), "tiles257": (4112, 16, 257), "tiles257_gridx1": (16, 4112, 257),
+                   "tiles513": (432, 304, 513), "tiles1": (16, 16, 1)}
+BIN_BATCH_SIZES = ((64, 48), (80, 48), (72, 41), (33, 17), (160, 16), (16, 160), (48, 48), (96, 64))
+
+
+def bits_to_z(bits):
+    return np.asarray(bits, np.uint32).view(np.float32).astype(np.float64)
+
+
+def _bin_spec(rng, W, H, P, z, two=0.15, big=0.02, cull_every=20, tile=None, empty=0.0):
+    """P splats on tile centres of a W x H image (`tile`: all on that one), a share `two` across a tile edge, a share `big`
+    wide (sigma 12), a share `empty` outside the image (a place in the depth order, no tile); every `cull_every`-th index (from
+    7 on) behind the near plane."""
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    t = rng.randint(0, gx * gy, P) if tile is None else np.broadcast_to(np.asarray(tile), (P,)).copy()
+    kind = rng.uniform(size=P)
+    x = 16.0 * (t % gx) + 7.5 + np.where((kind < two) & (gx > 1), 8.0, 0.0)
+    y = 16.0 * (t // gx) + 7.5
+    sig = np.where(kind > 1.0 - big, 12.0, 0.5)
+    x = np.where(rng.uniform(size=P) < empty, -400.0, x)
+    z = np.array(np.broadcast_to(z, (P,)), np.float64)
+    if cull_every:
+        z[7::cull_every] = 0.1
+    return dict(x=x, y=y, sig_a=sig, sig_b=sig, theta=np.zeros(P), opacity=np.full(P, 0.5), colour=rng.uniform(0.05, 0.95, (P, 3)), z=z)
+
+
+def binning_scene(name, P=None, W=64, H=48):
+    """The scenes of the binning edge tests, by name -> scene dict (splat_scene).
+      seam        P splats, random distinct-ish depths in [0.5, 40], 5 % behind the near plane interleaved by index
+      ties_one / ties3 / ties_low9 / ties_mid9   the same with one depth, three depths, keys that differ only in their lowest 9
+                  bits, only in bits 18-26 of (key - KEY27_BASE)
+      span / span_out   keys KEY27_BASE + 1 and KEY27_BASE + 2^27 - 3 among P = 300; span_out adds KEY27_BASE + 2^27 - 2
+      count<N>    N - 10 one-tile splats + 5 two-tile ones: N instances
+      cover       160 x 160, P = 600: two splats over all 100 tiles at depth ranks 255 and 256, the rest on one tile each
+      sparse      P = 5000, 80 % outside the image
+      onetile     P = 9000, every instance in tile 5 (40 distinct depths)
+      tiles<T>... (BIN_TILE_IMAGES) every tile of the image holds at least two one-tile splats"""
+    rng = np.random.RandomState(abs(hash_name(name + str(P))) % (2 ** 31))
+    zrand = lambda n: rng.uniform(0.5, 40.0, n).astype(np.float32).astype(np.float64)  # noqa: E731
+    if name == "seam":
+        spec = _bin_spec(rng, W, H, P, zrand(P))
+    elif name.startswith("ties"):
+        if name == "ties_one":
+            z = np.full(P, 3.25)
+        elif name == "ties3":
+            z = rng.choice([1.5, 3.25, 7.0], P)
+        elif name == "ties_low9":
+            z = bits_to_z(((KEY27_BASE + 0x100000) & ~0x1FF) + rng.randint(0, 512, P))
+        else:
+            z = bits_to_z(KEY27_BASE + 1 + (rng.randint(0, 512, P).astype(np.int64) << 18))
+        spec = _bin_spec(rng, W, H, P, z)
+    elif name in ("span", "span_out"):
+        P = 300
+        z = zrand(P)
+        z[11], z[12], z[200], z[201] = bits_to_z([KEY27_BASE + 1, KEY27_BASE + KEY27_SPAN - 3] * 2)
+        if name == "span_out":
+            z[100] = bits_to_z([KEY27_BASE + KEY27_SPAN - 2])[0]
+        spec = _bin_spec(rng, W, H, P, z, big=0.0, cull_every=0)
+        spec["x"][[11, 12, 100, 200, 201]], spec["y"][[11, 12, 100, 200, 201]] = 31.5, 23.5     # the image centre: four tiles
+    elif name.startswith("count"):
+        n = int(name[5:])
+        P = n - 5
+        spec = _bin_spec(rng, W, H, P, zrand(P), two=0.0, big=0.0, cull_every=0)
+        spec["x"][100:105] += 8.0 - 16.0 * (spec["x"][100:105] > W - 16)
+    elif name == "cover":
+        W, H, P = 160, 160, 600
+        rank = rng.permutation(P)
+        i255, i256 = int(np.nonzero(rank == 255)[0][0]), int(np.nonzero(rank == 256)[0][0])
+        spec = _bin_spec(rng, W, H, P, 1.0 + 0.01 * rank, two=0.0, big=0.0, cull_every=0)
+        spec["sig_a"][[i255, i256]] = spec["sig_b"][[i255, i256]] = 160.0
+    elif name == "sparse":
+        P = 5000
+        spec = _bin_spec(rng, W, H, P, zrand(P), empty=0.8)
+    elif name == "onetile":
+        P = 9000
+        spec = _bin_spec(rng, W, H, P, rng.choice(zrand(40), P), two=0.0, big=0.0, tile=5)
+    elif name in BIN_TILE_IMAGES:
+        W, H, T = BIN_TILE_IMAGES[name]
+        P = max(2 * T + 3, 40)
+        spec = _bin_spec(rng, W, H, P, zrand(P), two=0.0, big=0.0, cull_every=0, tile=rng.permutation(P) % T)
+    else:
+        raise KeyError(name)
+    return splat_scene(W, H, **spec)
+
+
+def binning_views(d, sizes, shifts=None):
+    """The Gaussians of scene d seen by cameras of other image sizes: same view matrix (so the same depth keys), moved by
+    shifts[k] = (dx, dz) in the view's own x / z (dz != 0: other keys; a huge dx: nothing on screen)."""
+    out = []
+    for k, (W, H) in enumerate(sizes):
+        e = splat_scene(W, H, [0.0], [0.0], 1.0, 1.0, 0.0, 0.5, [[0.5, 0.5, 0.5]], 2.0)
+        v = dict(d)
+        v.update({key: e[key] for key in ("viewmatrix", "projmatrix", "campos", "W", "H", "tanfovx", "tanfovy")})
+        dx, dz = (0.0, 0.0) if shifts is None else shifts[k]
+        if dx or dz:
+            vm = e["viewmatrix"].clone()
+            vm[3, 0], vm[3, 2] = -dx, dz
+            v["viewmatrix"], v["projmatrix"] = vm, vm @ e["projmatrix"]      # (the unmoved view matrix is the identity)
+            v["campos"] = torch.tensor([dx, 0.0, -dz])
+        out.append(v)
+    return out
+
+
+# What each case of the binning edge tests must hold; the tests assert it from the device state before anything is compared
+# (the populate functions of tests/test_gpu_binning_edges.py):
+#   "seam": "V < P (5 % culled), N > V (two-tile and wide splats), at most a few tied keys",
+#   "ties_one": "one distinct visible key", "ties3": "three distinct visible keys",
+#   "ties_low9": "keys equal above bit 9, > 256 distinct", "ties_mid9": "(key - KEY27_BASE) zero outside bits 18-26, > 256 distinct",
+#   "span": "min key KEY27_BASE + 1, max key KEY27_BASE + 2^27 - 3, both in the lists", "span_out": "max key KEY27_BASE + 2^27 - 2",
+#   "count<N>": "N instances, five Gaussians of two tiles", "cover": "two Gaussians of 100 tiles at depth ranks 255 and 256",
+#   "sparse": "V <= 0.25 P", "onetile": "one distinct tile id, N > 8192", "tiles<T>": "exactly T distinct tile ids",
