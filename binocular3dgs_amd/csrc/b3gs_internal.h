@@ -217,7 +217,8 @@ __device__ __forceinline__ uint32_t open_tiles(uint2 rc, const OpenMap& om) {
   return n;
 }
 
-// ---- wave and workgroup primitives of the feature modules (cloud, sweep, jpeg, metrics, frames, mesh, meshtools, knn) -------
+// ---- wave and workgroup primitives of the feature modules (cloud, sweep, jpeg, metrics, frames, mesh, meshtools, knn); the
+// ---- binning kernels use the wave ones (b3gs_wave_sum, b3gs_wave_scan) ----------------------------------------------------
 // One wave is 64 lanes; every lane of the wave (every thread of the workgroup, for the b3gs_block_* ones) makes the call.
 // xor butterfly 32, 16, .., 1: every lane gets the result, in one fixed tree (int, uint32_t, unsigned long long, float, double)
 template <typename T>
@@ -236,13 +237,13 @@ __device__ __forceinline__ float b3gs_wave_max(float v) {
   for (int d = B3GS_WAVE / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, B3GS_WAVE));
   return v;
 }
-// inclusive scan of one value per lane across the wave (int, uint32_t, unsigned long long; sums wrap)
-template <typename T>
-__device__ __forceinline__ T b3gs_wave_scan(T val, int lane) {
+// inclusive scan of one value per lane across the wave (int, uint32_t, unsigned long long; sums wrap); lane: int or unsigned
+template <typename T, typename L>
+__device__ __forceinline__ T b3gs_wave_scan(T val, L lane) {
 #pragma unroll
   for (int d = 1; d < B3GS_WAVE; d <<= 1) {
     const T o = __shfl_up(val, d, B3GS_WAVE);
-    if (lane >= d) val += o;
+    if (lane >= (L)d) val += o;
   }
   return val;
 }

@@ -10,6 +10,8 @@
 //      coalesced writes regardless of how many tiles one Gaussian covers),
 //   3. stable LSD radix sort of the N instances by tile id only (ceil(log2(tiles)/8) passes,
 //      2 at 800x600 and 1600x1600) -- stability keeps the depth/index order inside each tile.
+// Both sorts are passes of ONE kernel family (radix_hist / radix_rowscan / radix_scatter, templated on the digit width and
+// the radix tile size; radix_pass launches a pass): 8-bit digits, or -- depth keys inside a 27-bit span -- three 9-bit passes.
 // Resulting point_list is bit-identical to the 64-bit sort (tests/test_gpu_parity.py; at the radix / scan tile seams, with
 // tied depths, batched, shared and adopted orders, tight rects, capacity and two rounds: tests/test_gpu_binning_edges.py
 // against tests/binning_ref.py).
@@ -25,35 +27,26 @@
 #include "b3gs_internal.h"
 #include <utility>
 #include <cstdlib>
+#include <cassert>
 
 namespace {
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ u64 lanemask_lt() {
-  const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-}
 __device__ __forceinline__ unsigned lane_id() {
   return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }
-
-// inclusive scan across the 64 lanes of a wave
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const unsigned lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t o = __shfl_up(v, d, 64);
-    if (lane >= (unsigned)d) v += o;
-  }
-  return v;
+__device__ __forceinline__ u64 lanemask_lt(unsigned lane) {   // the lanes in front of lane_id()
+  return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 }
 
 // exclusive scan of one value per thread over a 256-thread workgroup (4 waves); returns the
 // exclusive prefix and writes the workgroup total to *total.  `tmp` is 8 words of LDS.
+// (Not b3gs_block_exscan: that one puts its barrier IN FRONT of the LDS write, this one behind the reads -- the scan and
+// emission kernels publish their own LDS tables through these barriers, so folding the two would move theirs.)
 __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* tmp, uint32_t* total) {
   const unsigned lane = lane_id(), w = threadIdx.x >> 6;
-  uint32_t inc = wave_incl_scan(v);
+  uint32_t inc = b3gs_wave_scan(v, lane);
   if (lane == 63) tmp[w] = inc;
   __syncthreads();
   uint32_t base = 0;
@@ -74,9 +67,9 @@ struct SortJob {
   uint32_t* vout;        // null: keys only (packed tile|index keys)
   const uint32_t* n_ptr; // null: n = n_cap
   uint32_t n_cap;
-  uint32_t nblk;
+  uint32_t nblk;         // radix tiles of n_cap elements, for the tile size of the pass (set by radix_pass)
   int32_t shift_base;    // added to the pass shift (position of the tile id inside a packed key)
-  uint32_t* hist;        // [256 * nblk] digit-major + 256 totals
+  uint32_t* hist;        // [digits * hist_stride(nblk)] digit-major + `digits` totals
   uint2* ranges;         // non-null on the LAST pass of the tile sort: per-tile [begin, end) by atomic min / max
   const uint32_t* off_ptr;   // null, or a device word: the n elements start at that offset of kin / vin / kout / vout
                              // (segment 2 of the tile lists sits behind segment 1 in the same arrays; ranges are absolute)
@@ -251,12 +244,6 @@ constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;  // 4096
 constexpr int SCAN_MAX_CHUNKS = 2048;
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-  return v;
-}
-
 // One pass gathers the rects in depth order (the random access of the binning), stores them sorted, and produces the
 // chunk sums AND the sums of every 256-Gaussian sub-block (iteration r of the strided loop = sub-block r): the emission
 // kernel scans inside its own sub-block, so no per-Gaussian offset array is written or read.
@@ -330,7 +317,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_chunk_sums(ScanBatch sb) {
   const int64_t begin = (int64_t)chunk * sb.tiles_per_chunk * SCAN_TILE;
   const int64_t end = min((int64_t)sb.P, begin + (int64_t)sb.tiles_per_chunk * SCAN_TILE);
   const unsigned lane = lane_id(), w = threadIdx.x >> 6;
-  const u64 lt = lanemask_lt();
+  const u64 lt = lanemask_lt(lane);
   uint32_t sum = 0, vis = 0, sum2 = 0, vis2 = 0;
   // the bitmaps of the tiles predicted open (304 bytes at 800x600) are staged in LDS when they fit
   OpenMap pa = job.pred, pb2 = pj.pred;
@@ -391,7 +378,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_chunk_sums(ScanBatch sb) {
           }
           ts_a += ta; vis += (ta != 0);
           ts_b += tb_; vis2 += (tb_ != 0);
-          const uint32_t wa = wave_sum(ta), wb = wave_sum(tb_);
+          const uint32_t wa = b3gs_wave_sum(ta), wb = b3gs_wave_sum(tb_);
           if (lane == 0) { ssub[0][w][t * SCAN_ITEMS + r] = wa; ssub[1][w][t * SCAN_ITEMS + r] = wb; }
         }
       }
@@ -421,7 +408,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_chunk_sums(ScanBatch sb) {
       BIN_TRACE(0, twg, 2, BIN_NOW());
       if (threadIdx.x < 64u) {   // 16 x 4 cells in depth order (sub-block major, then wave): exclusive prefix of their counts
         const uint32_t c = (uint32_t)__popcll(s_mask[threadIdx.x >> 2][threadIdx.x & 3u]);
-        const uint32_t inc = wave_incl_scan(c);
+        const uint32_t inc = b3gs_wave_scan(c, lane);
         s_base[threadIdx.x >> 2][threadIdx.x & 3u] = inc - c;
         if (threadIdx.x == 63u) s_H = inc;
       }
@@ -543,11 +530,13 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_chunk_offsets(ScanBatch sb)
 }
 
 // ---------------------------------------------------------------------------------------------
-// stable LSD radix pass on (u32 key, u32 value) pairs, 8-bit digit at `shift`
+// stable LSD radix pass on (u32 key, u32 value) pairs, digit of DIGIT_BITS bits at `shift`, radix tiles of ITEMS * 256 keys
 //   hist:    per-workgroup digit counts, stored digit-major  hist[d * nblk + blk]
 //   rowscan: one workgroup per digit: exclusive prefix over workgroups, digit total -> totals[d]
 //   scatter: wave-striped stable ranking (ballot match), LDS reorder, coalesced run writes
-// n is read from *n_ptr and clamped to n_cap.
+// ONE kernel family, two sets of instances: <8, B3GS_SORT_ITEMS> (depth sort over 32 bits, tile split, b3gs_launch_sort_u32_index:
+// n is read from *n_ptr and clamped to n_cap, the segment may start at *off_ptr, the last pass writes the tile ranges) and the
+// SPAN27 ones <9, 8 | 16> of the three-pass depth sort (key27 below).
 // (A single-launch chained-scan pass with decoupled look-back was measured on MI355X and is SLOWER
 //  here -- sort stage 352 us vs 274 us per view: a dependent kernel boundary costs ~1.5 us, an
 //  agent-scope hand-off 1-2 us PER look-back hop -- so the pass stays three launches.)
@@ -557,7 +546,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_chunk_offsets(ScanBatch sb)
 // CONSECUTIVE tiles are neighbours in the output; the histogram kernel leaves 16 bytes per digit row and four consecutive
 // workgroups complete a line.  With tile = workgroup id the neighbours land in eight different L2s and leave as partial
 // lines; with a contiguous band of tiles per XCD they meet in one L2 and leave as whole lines (round 5, same-box A/B at
-// the headline: radix9_scatter 27.4 -> 21.8 us; -DB3GS_SORT_NO_XCD_BANDS restores tile = workgroup id).
+// the headline: the 9-bit scatter 27.4 -> 21.8 us; -DB3GS_SORT_NO_XCD_BANDS restores tile = workgroup id).
 __device__ __forceinline__ bool xcd_band_tile(uint32_t g, uint32_t used, uint32_t* tile) {
 #ifndef B3GS_SORT_NO_XCD_BANDS
   const uint32_t per = (used + 7u) >> 3;
@@ -581,42 +570,90 @@ __device__ __forceinline__ bool xcd_band_tile(uint32_t g, uint32_t used, uint32_
 constexpr int HIST_TILES = 4;
 __host__ __device__ inline uint32_t hist_stride(uint32_t nblk) { return (nblk + 15u) & ~15u; }
 
-__global__ void __launch_bounds__(HIST_TILES * B3GS_SORT_THREADS) radix_hist(SortBatch sb, int pass_shift) {
-  __shared__ uint32_t h[HIST_TILES][256];
+// Depth sort in THREE passes of 9-bit digits (B3gsForwardView::depth_key_bits = 27).  A visible Gaussian has view z >
+// 0.2 (B3GS_NEAR), so its key -- the float bits of z -- is at least KEY27_BASE = bits(0.2f); keys of z up to ~13107
+// lie within 2^27 of it.  The first pass maps  key -> key - KEY27_BASE  (culled keys 0xFFFFFFFF -> 2^27 - 1, the
+// largest value) on the fly: order-preserving, ties keep their index order, so the resulting permutation is the one
+// the four 8-bit passes over all 32 bits produce.  The assumption is CHECKED, not trusted: the projection raises bit 1
+// of the caller's overflow word when a visible key falls outside the span (preprocess.hip), which drops that step on
+// the device like a capacity overflow and makes the host fall back to the full 32-bit sort.
+// SPAN27 instances serve these passes only: every job sorts its whole arrays (n = n_cap at offset 0, no n_ptr / off_ptr),
+// carries values and writes no ranges, and `xform` asks for the mapping -- none of which the other instances test for.
+constexpr uint32_t KEY27_BASE = 0x3E4CCCCDu;          // float bits of B3GS_NEAR
+constexpr uint32_t KEY27_SPAN = 1u << 27;
+__device__ __forceinline__ uint32_t key27(uint32_t k) {
+  if (k == 0xFFFFFFFFu) return KEY27_SPAN - 1u;       // culled: sinks to the end
+  const uint32_t d = k > KEY27_BASE ? k - KEY27_BASE : 0u;
+  return d < KEY27_SPAN - 2u ? d : KEY27_SPAN - 2u;   // (out-of-span keys are flagged by the projection)
+}
+
+// The elements a job sorts -- n of them from element `off` of its arrays -- and the radix tiles that hold them.  The grids
+// are sized by the CAPACITY (n lives on the device): workgroups past `used` do nothing, and the row scan / scatter only look
+// at the first `used` columns of the histogram.  SortJob::nblk is the host's tile count for the tile size of the pass.
+// ITEMS = keys per thread of a radix tile: 16 (4096-key tiles) for batches of views; 8 (2048-key tiles: twice the workgroups,
+// half the serial ranking rounds each) when ONE view is sorted alone and 245 tiles of 4096 would leave the CUs one
+// workgroup each (the reference-shaped surface renders view by view)
+struct SortSpan {
+  uint32_t off, n, used;
+};
+template <int ITEMS, bool SPAN27>
+__device__ __forceinline__ SortSpan sort_span(const SortJob& job) {
+  if (SPAN27) return SortSpan{0u, job.n_cap, job.nblk};
+  constexpr uint32_t TILE = ITEMS * B3GS_SORT_THREADS;
+  const uint32_t off = job.off_ptr ? min(*job.off_ptr, job.n_cap) : 0u;
+  const uint32_t n = job.n_ptr ? min(*job.n_ptr, job.n_cap - off) : job.n_cap - off;
+  return SortSpan{off, n, min(job.nblk, (uint32_t)(((uint64_t)n + TILE - 1) / TILE))};   // (64 bits: n + TILE - 1 wraps near 2^32)
+}
+
+// 256 threads (t = 0..255) count radix tile `blk` of a job into the 1 << DIGIT_BITS words of h
+template <int DIGIT_BITS, int ITEMS, bool SPAN27>
+__device__ __forceinline__ void radix_hist_tile(const SortJob& job, const SortSpan& sp, int pass_shift, int xform, uint32_t blk,
+                                                uint32_t t, uint32_t* h) {
+  constexpr uint32_t DIGITS = 1u << DIGIT_BITS;
+  const int shift = pass_shift + (SPAN27 ? 0 : job.shift_base);
+  const uint32_t* __restrict__ keys = job.kin + sp.off;
+#pragma unroll
+  for (uint32_t d = 0; d < DIGITS; d += 256) h[d + t] = 0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)blk * (ITEMS * B3GS_SORT_THREADS);
+#pragma unroll
+  for (int k = 0; k < ITEMS; k++) {
+    const uint64_t i = base + k * B3GS_SORT_THREADS + t;
+    if (i < sp.n) {
+      uint32_t kk = keys[i];
+      if (SPAN27 && xform) kk = key27(kk);
+      atomicAdd(&h[(kk >> shift) & (DIGITS - 1u)], 1u);
+    }
+  }
+  __syncthreads();
+}
+template <int DIGIT_BITS, int ITEMS, bool SPAN27>
+__global__ void __launch_bounds__(HIST_TILES * B3GS_SORT_THREADS) radix_hist(SortBatch sb, int pass_shift, int xform) {
+  constexpr uint32_t DIGITS = 1u << DIGIT_BITS;
+  __shared__ uint32_t h[HIST_TILES][DIGITS];
   const SortJob& job = sb.j[blockIdx.y];
   const uint32_t sub = threadIdx.x >> 8, t = threadIdx.x & 255u;
   if (sort_job_idle(job)) return;
-  const int shift = pass_shift + job.shift_base;
-  const uint32_t off = job.off_ptr ? min(*job.off_ptr, job.n_cap) : 0u;
-  const uint32_t* __restrict__ keys = job.kin + off;
-  const uint32_t n = job.n_ptr ? min(*job.n_ptr, job.n_cap - off) : job.n_cap - off;
-  // The grid is sized by the CAPACITY (n lives on the device); workgroups past n write nothing: row scan / scatter only
-  // look at the first ceil(n / tile) columns
-  const uint32_t used = min(job.nblk, (uint32_t)(((uint64_t)n + B3GS_SORT_TILE - 1) / B3GS_SORT_TILE));
+  const SortSpan sp = sort_span<ITEMS, SPAN27>(job);
   uint32_t grp;
-  if (!xcd_band_tile(blockIdx.x, (used + HIST_TILES - 1) / HIST_TILES, &grp)) return;
+  if (!xcd_band_tile(blockIdx.x, (sp.used + HIST_TILES - 1) / HIST_TILES, &grp)) return;
   const uint32_t blk0 = grp * HIST_TILES;
-  h[sub][t] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)(blk0 + sub) * B3GS_SORT_TILE;
+  radix_hist_tile<DIGIT_BITS, ITEMS, SPAN27>(job, sp, pass_shift, xform, blk0 + sub, t, h[sub]);
+  if (sub == 0) {
+    const uint32_t hs = hist_stride(job.nblk);
 #pragma unroll
-  for (int k = 0; k < B3GS_SORT_ITEMS; k++) {
-    const uint64_t i = base + k * B3GS_SORT_THREADS + t;
-    if (i < n) atomicAdd(&h[sub][(keys[i] >> shift) & 0xFF], 1u);
+    for (uint32_t d = t; d < DIGITS; d += 256)
+      *reinterpret_cast<uint4*>(job.hist + (size_t)d * hs + blk0) = make_uint4(h[0][d], h[1][d], h[2][d], h[3][d]);
   }
-  __syncthreads();
-  if (sub == 0)
-    *reinterpret_cast<uint4*>(job.hist + (size_t)t * hist_stride(job.nblk) + blk0) = make_uint4(h[0][t], h[1][t], h[2][t], h[3][t]);
 }
 
-__device__ __forceinline__ void radix_rowscan_body(const SortBatch& sb, uint32_t bx, uint32_t by, uint32_t* tmp) {
-  const SortJob& job = sb.j[by];
+// one workgroup of 256 threads per digit row
+template <int DIGIT_BITS, int ITEMS, bool SPAN27>
+__device__ __forceinline__ void radix_rowscan_body(const SortJob& job, uint32_t digit, uint32_t* tmp) {
   if (sort_job_idle(job)) return;
-  const uint32_t nblk = job.nblk;
-  const uint32_t off = job.off_ptr ? min(*job.off_ptr, job.n_cap) : 0u;
-  const uint32_t n = job.n_ptr ? min(*job.n_ptr, job.n_cap - off) : job.n_cap - off;
-  const uint32_t used = min(nblk, (uint32_t)(((uint64_t)n + B3GS_SORT_TILE - 1) / B3GS_SORT_TILE));   // columns the histogram pass wrote
-  uint32_t* row = job.hist + (size_t)bx * hist_stride(nblk);
+  const uint32_t used = sort_span<ITEMS, SPAN27>(job).used;   // columns the histogram pass wrote
+  const uint32_t hs = hist_stride(job.nblk);
+  uint32_t* row = job.hist + (size_t)digit * hs;
   uint32_t carry = 0;
   for (uint32_t b0 = 0; b0 < used; b0 += 256) {
     uint32_t i = b0 + threadIdx.x;
@@ -626,71 +663,81 @@ __device__ __forceinline__ void radix_rowscan_body(const SortBatch& sb, uint32_t
     if (i < used) row[i] = carry + ex;
     carry += tot;
   }
-  if (threadIdx.x == 0) job.hist[(size_t)256 * hist_stride(nblk) + bx] = carry;  // totals
+  if (threadIdx.x == 0) job.hist[(size_t)(1u << DIGIT_BITS) * hs + digit] = carry;  // totals
 }
+template <int DIGIT_BITS, int ITEMS, bool SPAN27>
 __global__ void __launch_bounds__(256) radix_rowscan(SortBatch sb) {
   __shared__ uint32_t tmp[8];
-  radix_rowscan_body(sb, blockIdx.x, blockIdx.y, tmp);
+  radix_rowscan_body<DIGIT_BITS, ITEMS, SPAN27>(sb.j[blockIdx.y], blockIdx.x, tmp);
 }
 
 // HAS_VAL = false: keys only (packed tile|index words): no value staging buffer, 22 KB instead of 38 KB of LDS
 // per workgroup (7 instead of 4 workgroups per CU)
 // BITS: significant bits of this pass's digit (the last tile-split pass sees only the top bits of the tile id: 3 at
 // 800x600) -- the ballot ranking costs one round per bit
-template <bool HAS_VAL>
+template <int DIGIT_BITS, int ITEMS, bool HAS_VAL>
 struct ScatterShared {
-  uint32_t wave_cnt[4][256];
-  uint32_t blk_start[256];  // first slot of digit d inside this workgroup's reorder buffer
-  uint32_t gbase[256];      // global destination of that first slot
+  static constexpr int DIGITS = 1 << DIGIT_BITS, TILE = ITEMS * B3GS_SORT_THREADS;
+  uint32_t wave_cnt[4][DIGITS];
+  uint32_t blk_start[DIGITS];  // first slot of digit d inside this workgroup's reorder buffer
+  uint32_t gbase[DIGITS];      // global destination of that first slot
   uint32_t tmp[8];
-  uint32_t s_key[B3GS_SORT_TILE];
-  uint32_t s_val[HAS_VAL ? B3GS_SORT_TILE : 1];
+  uint32_t s_key[TILE];
+  uint32_t s_val[HAS_VAL ? TILE : 1];
 };
-// (bx, by) = (radix tile, job): blockIdx of the stand-alone launch, a loop index inside the repair kernel
-template <bool HAS_VAL, int BITS>
-__device__ __forceinline__ void radix_scatter_body(const SortBatch& sb, int pass_shift, uint32_t bx, uint32_t by,
-                                                   ScatterShared<HAS_VAL>& sh) {
-  uint32_t (&wave_cnt)[4][256] = sh.wave_cnt;
-  uint32_t (&blk_start)[256] = sh.blk_start;
-  uint32_t (&gbase)[256] = sh.gbase;
+// bx = radix tile of the job: from blockIdx of the stand-alone launch, a loop index inside the repair kernel
+template <int DIGIT_BITS, int ITEMS, bool HAS_VAL, int BITS, bool SPAN27>
+__device__ __forceinline__ void radix_scatter_body(const SortJob& job, int pass_shift, int xform, uint32_t bx,
+                                                   ScatterShared<DIGIT_BITS, ITEMS, HAS_VAL>& sh) {
+  constexpr uint32_t DIGITS = 1u << DIGIT_BITS, TILE = ITEMS * B3GS_SORT_THREADS;
+  constexpr int DPT = DIGITS / B3GS_SORT_THREADS;   // digits per thread: thread t owns digits t, t + 256, ...
+  static_assert(DPT >= 1 && BITS <= DIGIT_BITS && (HAS_VAL || !SPAN27), "radix_scatter_body");
+  uint32_t (&wave_cnt)[4][DIGITS] = sh.wave_cnt;
+  uint32_t (&blk_start)[DIGITS] = sh.blk_start;
+  uint32_t (&gbase)[DIGITS] = sh.gbase;
   uint32_t (&tmp)[8] = sh.tmp;
-  uint32_t (&s_key)[B3GS_SORT_TILE] = sh.s_key;
-  uint32_t (&s_val)[HAS_VAL ? B3GS_SORT_TILE : 1] = sh.s_val;
+  uint32_t (&s_key)[TILE] = sh.s_key;
+  uint32_t (&s_val)[HAS_VAL ? TILE : 1] = sh.s_val;
 
-  const SortJob& job = sb.j[by];
-  if (bx >= job.nblk || sort_job_idle(job)) return;
-  const int shift = pass_shift + job.shift_base;
-  const uint32_t off = job.off_ptr ? min(*job.off_ptr, job.n_cap) : 0u;
+  if (sort_job_idle(job)) return;
+  const SortSpan sp = sort_span<ITEMS, SPAN27>(job);
+  if (bx >= sp.used) return;  // uniform per workgroup
+  const int shift = pass_shift + (SPAN27 ? 0 : job.shift_base);
+  const uint32_t off = sp.off, n = sp.n;
   const uint32_t* __restrict__ keys_in = job.kin + off;
   const uint32_t* __restrict__ vals_in = job.vin ? job.vin + off : nullptr;
   uint32_t* __restrict__ keys_out = job.kout + off;
   uint32_t* __restrict__ vals_out = job.vout ? job.vout + off : nullptr;
-  const uint32_t nblk = job.nblk;
+  const bool want_val = SPAN27 || vals_out != nullptr;   // (HAS_VAL instances also serve batches with a keys-only job)
   const uint32_t* __restrict__ hist = job.hist;
-  const uint32_t hstride = hist_stride(nblk);
-  const uint32_t* __restrict__ totals = job.hist + (size_t)256 * hstride;
-  const uint32_t n = job.n_ptr ? min(*job.n_ptr, job.n_cap - off) : job.n_cap - off;
-  const uint32_t tile_base = bx * B3GS_SORT_TILE;
-  if (tile_base >= n) return;  // uniform per workgroup
-  const uint32_t tile_n = min((uint32_t)B3GS_SORT_TILE, n - tile_base);
+  const uint32_t hstride = hist_stride(job.nblk);
+  const uint32_t* __restrict__ totals = job.hist + (size_t)DIGITS * hstride;
+  const uint32_t tile_base = bx * TILE;
+  const uint32_t tile_n = min(TILE, n - tile_base);
   const unsigned lane = lane_id(), w = threadIdx.x >> 6;
-  const u64 lt = lanemask_lt();
+  const u64 lt = lanemask_lt(lane);
 
 #pragma unroll
-  for (int k = 0; k < 4; k++) wave_cnt[k][threadIdx.x] = 0;
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int h = 0; h < DPT; h++) wave_cnt[k][threadIdx.x + 256 * h] = 0;
   __syncthreads();
 
-  // wave w owns the contiguous slab [w*1024, (w+1)*1024) of the tile, 16 rounds of 64
-  uint32_t key[B3GS_SORT_ITEMS], val[B3GS_SORT_ITEMS], rank[B3GS_SORT_ITEMS];
+  // wave w owns the contiguous slab [w ITEMS 64, (w + 1) ITEMS 64) of the tile, ITEMS rounds of 64
+  uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
   WaveFlags wf{0ull, 0ull};
-  if (HAS_VAL && vals_out && !vals_in) wf = load_wave_flags(job, tile_base + w * (B3GS_SORT_ITEMS * 64), B3GS_SORT_ITEMS, n, lane);
-  sort_load_rows<HAS_VAL>(std::make_integer_sequence<int, B3GS_SORT_ITEMS>{}, key, val, keys_in, vals_in, vals_out != nullptr, wf,
-                          tile_base, tile_n, w, lane);
+  if (HAS_VAL && want_val && !vals_in) wf = load_wave_flags(job, tile_base + w * (ITEMS * 64), ITEMS, n, lane);
+  sort_load_rows<HAS_VAL>(std::make_integer_sequence<int, ITEMS>{}, key, val, keys_in, vals_in, want_val, wf, tile_base, tile_n, w, lane);
+  if (SPAN27 && xform) {
 #pragma unroll
-  for (int r = 0; r < B3GS_SORT_ITEMS; r++) {
-    const uint32_t li = w * (B3GS_SORT_ITEMS * 64) + r * 64 + lane;
+    for (int r = 0; r < ITEMS; r++)
+      if (w * (ITEMS * 64) + r * 64 + lane < tile_n) key[r] = key27(key[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < ITEMS; r++) {
+    const uint32_t li = w * (ITEMS * 64) + r * 64 + lane;
     const bool valid = li < tile_n;
-    const uint32_t d = (key[r] >> shift) & 0xFF;
+    const uint32_t d = (key[r] >> shift) & (DIGITS - 1u);
     u64 m = __ballot(valid);
 #pragma unroll
     for (int b = 0; b < BITS; b++) {
@@ -708,44 +755,60 @@ __device__ __forceinline__ void radix_scatter_body(const SortBatch& sb, int pass
   }
   __syncthreads();
 
-  // per digit (thread = digit): exclusive prefix over the 4 waves, workgroup digit start, global base
+  // per digit: exclusive prefix over the 4 waves, workgroup digit start, global base; digit t + 256 h comes behind all the
+  // digits of the groups h' < h
   {
-    const uint32_t d = threadIdx.x;
-    uint32_t c0 = wave_cnt[0][d], c1 = wave_cnt[1][d], c2 = wave_cnt[2][d], c3 = wave_cnt[3][d];
-    uint32_t tot = c0 + c1 + c2 + c3, dummy;
-    uint32_t start = block_excl_scan_256(tot, tmp, &dummy);
-    uint32_t dig_total = totals[d], dummy2;
-    uint32_t dig_base = block_excl_scan_256(dig_total, tmp, &dummy2);
-    wave_cnt[0][d] = start;
-    wave_cnt[1][d] = start + c0;
-    wave_cnt[2][d] = start + c0 + c1;
-    wave_cnt[3][d] = start + c0 + c1 + c2;
-    blk_start[d] = start;
-    gbase[d] = dig_base + hist[(size_t)d * hstride + bx];
+    uint32_t c[DPT][4], tot[DPT], dt[DPT], start[DPT], dbase[DPT];
+#pragma unroll
+    for (int h = 0; h < DPT; h++) {
+      const uint32_t d = threadIdx.x + 256u * h;
+#pragma unroll
+      for (int k = 0; k < 4; k++) c[h][k] = wave_cnt[k][d];
+      tot[h] = (c[h][0] + c[h][1]) + (c[h][2] + c[h][3]);
+      dt[h] = totals[d];
+    }
+    uint32_t behind = 0, gbehind = 0, all;
+#pragma unroll
+    for (int h = 0; h < DPT; h++) {
+      start[h] = behind + block_excl_scan_256(tot[h], tmp, &all);
+      behind += all;
+      dbase[h] = gbehind + block_excl_scan_256(dt[h], tmp, &all);
+      gbehind += all;
+    }
+#pragma unroll
+    for (int h = 0; h < DPT; h++) {
+      const uint32_t d = threadIdx.x + 256u * h;
+      wave_cnt[0][d] = start[h];
+      wave_cnt[1][d] = start[h] + c[h][0];
+      wave_cnt[2][d] = start[h] + c[h][0] + c[h][1];
+      wave_cnt[3][d] = start[h] + c[h][0] + c[h][1] + c[h][2];
+      blk_start[d] = start[h];
+      gbase[d] = dbase[h] + hist[(size_t)d * hstride + bx];
+    }
   }
   __syncthreads();
 
 #pragma unroll
-  for (int r = 0; r < B3GS_SORT_ITEMS; r++) {
-    const uint32_t li = w * (B3GS_SORT_ITEMS * 64) + r * 64 + lane;
+  for (int r = 0; r < ITEMS; r++) {
+    const uint32_t li = w * (ITEMS * 64) + r * 64 + lane;
     if (li < tile_n) {
-      const uint32_t d = (key[r] >> shift) & 0xFF;
+      const uint32_t d = (key[r] >> shift) & (DIGITS - 1u);
       const uint32_t p = wave_cnt[w][d] + rank[r];
       s_key[p] = key[r];
-      if (HAS_VAL && vals_out) s_val[p] = val[r];
+      if (HAS_VAL && want_val) s_val[p] = val[r];
     }
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < B3GS_SORT_ITEMS; k++) {
+  for (int k = 0; k < ITEMS; k++) {
     const uint32_t p = k * B3GS_SORT_THREADS + threadIdx.x;
     if (p < tile_n) {
       const uint32_t kk = s_key[p];
-      const uint32_t d = (kk >> shift) & 0xFF;
+      const uint32_t d = (kk >> shift) & (DIGITS - 1u);
       const uint32_t dst = gbase[d] + (p - blk_start[d]);
       keys_out[dst] = kk;
-      if (HAS_VAL && vals_out) vals_out[dst] = s_val[p];
-      if (job.ranges) {
+      if (HAS_VAL && want_val) vals_out[dst] = s_val[p];
+      if (!SPAN27 && job.ranges) {
         // Last pass: the keys of one tile are contiguous in this workgroup's reorder buffer (grouped by the
         // top digit, ordered by the lower ones from the earlier passes) and land on consecutive addresses,
         // so run boundaries give the tile's range inside this workgroup; min / max merge the workgroups
@@ -757,204 +820,14 @@ __device__ __forceinline__ void radix_scatter_body(const SortBatch& sb, int pass
     }
   }
 }
-template <bool HAS_VAL, int BITS>
-__global__ void __launch_bounds__(B3GS_SORT_THREADS) radix_scatter(SortBatch sb, int pass_shift) {
-  __shared__ ScatterShared<HAS_VAL> sh;
+template <int DIGIT_BITS, int ITEMS, bool HAS_VAL, int BITS, bool SPAN27>
+__global__ void __launch_bounds__(B3GS_SORT_THREADS) radix_scatter(SortBatch sb, int pass_shift, int xform) {
+  __shared__ ScatterShared<DIGIT_BITS, ITEMS, HAS_VAL> sh;
   const SortJob& job = sb.j[blockIdx.y];
-  if (sort_job_idle(job)) return;      // (a gated-off job's pointers are not read; the body checked this first)
-  const uint32_t off = job.off_ptr ? min(*job.off_ptr, job.n_cap) : 0u;
-  const uint32_t n = job.n_ptr ? min(*job.n_ptr, job.n_cap - off) : job.n_cap - off;
+  if (sort_job_idle(job)) return;      // (a gated-off job's pointers are not read)
   uint32_t tile;
-  // (tile count in 64 bits like radix_hist: n + tile - 1 must not wrap for n near 2^32)
-  if (!xcd_band_tile(blockIdx.x, min(job.nblk, (uint32_t)(((uint64_t)n + B3GS_SORT_TILE - 1) / B3GS_SORT_TILE)), &tile)) return;
-  radix_scatter_body<HAS_VAL, BITS>(sb, pass_shift, tile, blockIdx.y, sh);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Depth sort in THREE passes of 9-bit digits (B3gsForwardView::depth_key_bits = 27).  A visible Gaussian has view z >
-// 0.2 (B3GS_NEAR), so its key -- the float bits of z -- is at least KEY27_BASE = bits(0.2f); keys of z up to ~13107
-// lie within 2^27 of it.  The first pass maps  key -> key - KEY27_BASE  (culled keys 0xFFFFFFFF -> 2^27 - 1, the
-// largest value) on the fly: order-preserving, ties keep their index order, so the resulting permutation is the one
-// the four 8-bit passes over all 32 bits produce.  The assumption is CHECKED, not trusted: the projection raises bit 1
-// of the caller's overflow word when a visible key falls outside the span (preprocess.hip), which drops that step on
-// the device like a capacity overflow and makes the host fall back to the full 32-bit sort.
-// Same structure as the 8-bit kernels above with 512 digits (thread t owns digits t and t + 256).
-// ---------------------------------------------------------------------------------------------
-constexpr uint32_t KEY27_BASE = 0x3E4CCCCDu;          // float bits of B3GS_NEAR
-constexpr uint32_t KEY27_SPAN = 1u << 27;
-__device__ __forceinline__ uint32_t key27(uint32_t k) {
-  if (k == 0xFFFFFFFFu) return KEY27_SPAN - 1u;       // culled: sinks to the end
-  const uint32_t d = k > KEY27_BASE ? k - KEY27_BASE : 0u;
-  return d < KEY27_SPAN - 2u ? d : KEY27_SPAN - 2u;   // (out-of-span keys are flagged by the projection)
-}
-
-// ITEMS = keys per thread of a radix tile: 16 (4096-key tiles) for batches of views; 8 (2048-key tiles: twice the workgroups,
-// half the serial ranking rounds each) when ONE view is sorted alone and 245 tiles of 4096 would leave the CUs one
-// workgroup each (the reference-shaped surface renders view by view)
-template <int ITEMS>
-__global__ void __launch_bounds__(HIST_TILES * B3GS_SORT_THREADS) radix9_hist(SortBatch sb, int shift, int xform) {
-  constexpr uint32_t TILE = ITEMS * B3GS_SORT_THREADS;
-  __shared__ uint32_t h[HIST_TILES][512];
-  const SortJob& job = sb.j[blockIdx.y];
-  const uint32_t sub = threadIdx.x >> 8, t = threadIdx.x & 255u;
-  const uint32_t nblk = (job.n_cap + TILE - 1) / TILE;
-  uint32_t grp;
-  if (!xcd_band_tile(blockIdx.x, (nblk + HIST_TILES - 1) / HIST_TILES, &grp) || sort_job_idle(job)) return;
-  const uint32_t blk0 = grp * HIST_TILES;
-  const uint32_t* __restrict__ keys = job.kin;
-  const uint32_t n = job.n_cap;
-  if ((uint64_t)blk0 * TILE >= n) return;
-  h[sub][t] = 0;
-  h[sub][t + 256] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)(blk0 + sub) * TILE;
-#pragma unroll
-  for (int k = 0; k < ITEMS; k++) {
-    const uint64_t i = base + k * B3GS_SORT_THREADS + t;
-    if (i < n) {
-      uint32_t kk = keys[i];
-      if (xform) kk = key27(kk);
-      atomicAdd(&h[sub][(kk >> shift) & 0x1FF], 1u);
-    }
-  }
-  __syncthreads();
-  if (sub == 0) {
-    const uint32_t hs = hist_stride(nblk);
-    *reinterpret_cast<uint4*>(job.hist + (size_t)t * hs + blk0) = make_uint4(h[0][t], h[1][t], h[2][t], h[3][t]);
-    *reinterpret_cast<uint4*>(job.hist + (size_t)(t + 256) * hs + blk0) =
-        make_uint4(h[0][t + 256], h[1][t + 256], h[2][t + 256], h[3][t + 256]);
-  }
-}
-
-template <int ITEMS>
-__global__ void __launch_bounds__(256) radix9_rowscan(SortBatch sb) {
-  __shared__ uint32_t tmp[8];
-  constexpr uint32_t TILE = ITEMS * B3GS_SORT_THREADS;
-  const SortJob& job = sb.j[blockIdx.y];
-  if (sort_job_idle(job)) return;
-  const uint32_t nblk = (job.n_cap + TILE - 1) / TILE;
-  const uint32_t used = nblk;
-  uint32_t* row = job.hist + (size_t)blockIdx.x * hist_stride(nblk);
-  uint32_t carry = 0;
-  for (uint32_t b0 = 0; b0 < used; b0 += 256) {
-    uint32_t i = b0 + threadIdx.x;
-    uint32_t v = i < used ? row[i] : 0u;
-    uint32_t tot;
-    uint32_t ex = block_excl_scan_256(v, tmp, &tot);
-    if (i < used) row[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) job.hist[(size_t)512 * hist_stride(nblk) + blockIdx.x] = carry;  // totals
-}
-
-template <int ITEMS>
-__global__ void __launch_bounds__(B3GS_SORT_THREADS) radix9_scatter(SortBatch sb, int shift, int xform) {
-  constexpr uint32_t TILE = ITEMS * B3GS_SORT_THREADS;
-  __shared__ uint32_t wave_cnt[4][512];
-  __shared__ uint32_t blk_start[512];
-  __shared__ uint32_t gbase[512];
-  __shared__ uint32_t tmp[8];
-  __shared__ uint32_t s_key[TILE];
-  __shared__ uint32_t s_val[TILE];
-  const SortJob& job = sb.j[blockIdx.y];
-  const uint32_t nblk = (job.n_cap + TILE - 1) / TILE;
-  uint32_t bx;
-  if (!xcd_band_tile(blockIdx.x, nblk, &bx) || sort_job_idle(job)) return;
-  const uint32_t* __restrict__ keys_in = job.kin;
-  const uint32_t* __restrict__ vals_in = job.vin;
-  uint32_t* __restrict__ keys_out = job.kout;
-  uint32_t* __restrict__ vals_out = job.vout;
-  const uint32_t* __restrict__ hist = job.hist;
-  const uint32_t hstride = hist_stride(nblk);
-  const uint32_t* __restrict__ totals = job.hist + (size_t)512 * hstride;
-  const uint32_t n = job.n_cap;
-  const uint32_t tile_base = bx * TILE;
-  if (tile_base >= n) return;
-  const uint32_t tile_n = min(TILE, n - tile_base);
-  const unsigned lane = lane_id(), w = threadIdx.x >> 6;
-  const u64 lt = lanemask_lt();
-#pragma unroll
-  for (int k = 0; k < 4; k++) { wave_cnt[k][threadIdx.x] = 0; wave_cnt[k][threadIdx.x + 256] = 0; }
-  __syncthreads();
-  uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
-  WaveFlags wf{0ull, 0ull};
-  if (!vals_in) wf = load_wave_flags(job, tile_base + w * (ITEMS * 64), ITEMS, n, lane);
-  sort_load_rows<true>(std::make_integer_sequence<int, ITEMS>{}, key, val, keys_in, vals_in, true, wf, tile_base, tile_n, w, lane);
-  if (xform) {
-#pragma unroll
-    for (int r = 0; r < ITEMS; r++)
-      if (w * (ITEMS * 64) + r * 64 + lane < tile_n) key[r] = key27(key[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < ITEMS; r++) {
-    const uint32_t li = w * (ITEMS * 64) + r * 64 + lane;
-    const bool valid = li < tile_n;
-    const uint32_t d = (key[r] >> shift) & 0x1FF;
-    u64 m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 9; b++) {
-      const bool bit = (d >> b) & 1u;
-      const u64 bal = __ballot(bit);
-      m &= bit ? bal : ~bal;
-    }
-    const uint32_t before = (uint32_t)__popcll(m & lt);
-    const uint32_t cnt = wave_cnt[w][d];
-    rank[r] = cnt + before;
-    __builtin_amdgcn_wave_barrier();
-    if (valid && before == 0) wave_cnt[w][d] = cnt + (uint32_t)__popcll(m);
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  {   // per digit (thread t owns digits t and t + 256): prefix over the 4 waves, workgroup digit start, global base
-    uint32_t c[2][4], tot[2], dt[2];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const uint32_t d = threadIdx.x + 256u * h;
-#pragma unroll
-      for (int k = 0; k < 4; k++) c[h][k] = wave_cnt[k][d];
-      tot[h] = (c[h][0] + c[h][1]) + (c[h][2] + c[h][3]);
-      dt[h] = totals[d];
-    }
-    uint32_t lo_tot, hi_tot, lo_dtot, hi_dtot;
-    const uint32_t s0 = block_excl_scan_256(tot[0], tmp, &lo_tot);
-    const uint32_t s1 = block_excl_scan_256(tot[1], tmp, &hi_tot) + lo_tot;
-    const uint32_t g0 = block_excl_scan_256(dt[0], tmp, &lo_dtot);
-    const uint32_t g1 = block_excl_scan_256(dt[1], tmp, &hi_dtot) + lo_dtot;
-    const uint32_t start[2] = {s0, s1}, dbase[2] = {g0, g1};
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const uint32_t d = threadIdx.x + 256u * h;
-      wave_cnt[0][d] = start[h];
-      wave_cnt[1][d] = start[h] + c[h][0];
-      wave_cnt[2][d] = start[h] + c[h][0] + c[h][1];
-      wave_cnt[3][d] = start[h] + c[h][0] + c[h][1] + c[h][2];
-      blk_start[d] = start[h];
-      gbase[d] = dbase[h] + hist[(size_t)d * hstride + bx];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < ITEMS; r++) {
-    const uint32_t li = w * (ITEMS * 64) + r * 64 + lane;
-    if (li < tile_n) {
-      const uint32_t d = (key[r] >> shift) & 0x1FF;
-      const uint32_t p = wave_cnt[w][d] + rank[r];
-      s_key[p] = key[r];
-      s_val[p] = val[r];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < ITEMS; k++) {
-    const uint32_t p = k * B3GS_SORT_THREADS + threadIdx.x;
-    if (p < tile_n) {
-      const uint32_t kk = s_key[p];
-      const uint32_t d = (kk >> shift) & 0x1FF;
-      const uint32_t dst = gbase[d] + (p - blk_start[d]);
-      keys_out[dst] = kk;
-      vals_out[dst] = s_val[p];
-    }
-  }
+  if (!xcd_band_tile(blockIdx.x, sort_span<ITEMS, SPAN27>(job).used, &tile)) return;
+  radix_scatter_body<DIGIT_BITS, ITEMS, HAS_VAL, BITS, SPAN27>(job, pass_shift, xform, tile, sh);
 }
 
 // ABI 7: a view whose depth keys all equal those of an earlier forward (B3gsForwardView::depth_order_hint) takes that
@@ -1001,47 +874,49 @@ __global__ void __launch_bounds__(256) adopt_order_kernel(AdoptBatch ab) {
   }
 }
 
-// one 9-bit pass over all jobs (depth keys only: every job has values, n = n_cap = P)
-template <int ITEMS>
-void radix9_pass_t(SortBatch& sb, int shift, bool xform, hipStream_t s) {
+// One pass over all jobs: three launches.  It sets every job's nblk for its tile size and otherwise leaves the jobs as they
+// are: the CALLER swaps in / out before the next pass.
+// `bits`: how many bits of the digit at `shift` can be non-zero in any key of the batch (all of them unless the caller knows)
+using SortKernel = void (*)(SortBatch, int, int);
+template <int DIGIT_BITS, int ITEMS, bool HAS_VAL>
+SortKernel scatter_for_bits(int bits) {
+  return bits <= 2   ? radix_scatter<DIGIT_BITS, ITEMS, HAS_VAL, 2, false>
+         : bits <= 4 ? radix_scatter<DIGIT_BITS, ITEMS, HAS_VAL, 4, false>
+         : bits <= 6 ? radix_scatter<DIGIT_BITS, ITEMS, HAS_VAL, 6, false>
+                     : radix_scatter<DIGIT_BITS, ITEMS, HAS_VAL, DIGIT_BITS, false>;
+}
+template <int DIGIT_BITS, int ITEMS, bool SPAN27>
+void radix_pass_t(SortBatch& sb, int shift, int bits, bool xform, hipStream_t s) {
+  constexpr uint32_t TILE = ITEMS * B3GS_SORT_THREADS;
   uint32_t max_blk = 0;
+  bool any_val = false;
   for (int k = 0; k < sb.n; k++) {
-    const uint32_t nb = (sb.j[k].n_cap + ITEMS * B3GS_SORT_THREADS - 1) / (ITEMS * B3GS_SORT_THREADS);
-    max_blk = nb > max_blk ? nb : max_blk;
+    sb.j[k].nblk = (uint32_t)(((uint64_t)sb.j[k].n_cap + TILE - 1) / TILE);
+    max_blk = sb.j[k].nblk > max_blk ? sb.j[k].nblk : max_blk;
+    any_val = any_val || sb.j[k].vout != nullptr;
+    // what the SPAN27 instances do not test for (sort_span, radix_scatter_body)
+    assert(!SPAN27 || (!sb.j[k].n_ptr && !sb.j[k].off_ptr && !sb.j[k].ranges && sb.j[k].vout && sb.j[k].shift_base == 0));
   }
   if (sb.n <= 0 || max_blk == 0) return;
-  hipLaunchKernelGGL(radix9_hist<ITEMS>, dim3(B3GS_SORT_GRID_X((max_blk + HIST_TILES - 1) / HIST_TILES), sb.n), dim3(HIST_TILES * B3GS_SORT_THREADS),
-                     0, s, sb, shift, xform ? 1 : 0);
-  hipLaunchKernelGGL(radix9_rowscan<ITEMS>, dim3(512, sb.n), dim3(256), 0, s, sb);
-  hipLaunchKernelGGL(radix9_scatter<ITEMS>, dim3(B3GS_SORT_GRID_X(max_blk), sb.n), dim3(B3GS_SORT_THREADS), 0, s, sb, shift, xform ? 1 : 0);
+  const int xf = xform ? 1 : 0;
+  hipLaunchKernelGGL((radix_hist<DIGIT_BITS, ITEMS, SPAN27>), dim3(B3GS_SORT_GRID_X((max_blk + HIST_TILES - 1) / HIST_TILES), sb.n),
+                     dim3(HIST_TILES * B3GS_SORT_THREADS), 0, s, sb, shift, xf);
+  hipLaunchKernelGGL((radix_rowscan<DIGIT_BITS, ITEMS, SPAN27>), dim3(1 << DIGIT_BITS, sb.n), dim3(256), 0, s, sb);
+  SortKernel scatter;
+  if constexpr (SPAN27) scatter = radix_scatter<DIGIT_BITS, ITEMS, true, DIGIT_BITS, true>;
+  else scatter = any_val ? scatter_for_bits<DIGIT_BITS, ITEMS, true>(bits) : scatter_for_bits<DIGIT_BITS, ITEMS, false>(bits);
+  hipLaunchKernelGGL(scatter, dim3(B3GS_SORT_GRID_X(max_blk), sb.n), dim3(B3GS_SORT_THREADS), 0, s, sb, shift, xf);
 }
-void radix9_pass(SortBatch& sb, int shift, bool xform, hipStream_t s) {
-  static const int force = getenv("B3GS_SORT9_ITEMS") ? atoi(getenv("B3GS_SORT9_ITEMS")) : 0;   // (A/B switch)
-  const int items = force ? force : (sb.n == 1 ? 8 : 16);
-  if (items == 8) radix9_pass_t<8>(sb, shift, xform, s);
-  else radix9_pass_t<16>(sb, shift, xform, s);
-}
-
-// one pass over all jobs (radix_pass below); it leaves the jobs as they are: the CALLER swaps in / out before the next pass
-template <int BITS>
-void launch_scatter(const SortBatch& sb, bool any_val, uint32_t max_blk, int shift, hipStream_t s) {
-  if (any_val) hipLaunchKernelGGL((radix_scatter<true, BITS>), dim3(B3GS_SORT_GRID_X(max_blk), sb.n), dim3(B3GS_SORT_THREADS), 0, s, sb, shift);
-  else hipLaunchKernelGGL((radix_scatter<false, BITS>), dim3(B3GS_SORT_GRID_X(max_blk), sb.n), dim3(B3GS_SORT_THREADS), 0, s, sb, shift);
-}
-
-// `bits`: how many bits of the digit at `shift` can be non-zero in any key of the batch (8 unless the caller knows)
+// the 8-bit pass of the depth sort over 32 bits, the tile split and b3gs_launch_sort_u32_index ...
 void radix_pass(SortBatch& sb, int shift, hipStream_t s, int bits = 8) {
-  uint32_t max_blk = 0;
-  for (int k = 0; k < sb.n; k++) max_blk = sb.j[k].nblk > max_blk ? sb.j[k].nblk : max_blk;
-  if (sb.n <= 0 || max_blk == 0) return;
-  hipLaunchKernelGGL(radix_hist, dim3(B3GS_SORT_GRID_X((max_blk + HIST_TILES - 1) / HIST_TILES), sb.n), dim3(HIST_TILES * B3GS_SORT_THREADS), 0, s, sb, shift);
-  hipLaunchKernelGGL(radix_rowscan, dim3(256, sb.n), dim3(256), 0, s, sb);
-  bool any_val = false;
-  for (int k = 0; k < sb.n; k++) any_val = any_val || sb.j[k].vout != nullptr;
-  if (bits <= 2) launch_scatter<2>(sb, any_val, max_blk, shift, s);
-  else if (bits <= 4) launch_scatter<4>(sb, any_val, max_blk, shift, s);
-  else if (bits <= 6) launch_scatter<6>(sb, any_val, max_blk, shift, s);
-  else launch_scatter<8>(sb, any_val, max_blk, shift, s);
+  radix_pass_t<8, B3GS_SORT_ITEMS, false>(sb, shift, bits, false, s);
+}
+// ... and a 9-bit pass of the three-pass depth sort (every job has values, n = n_cap = P; xform on its first pass), in
+// 2048-key tiles when one view is sorted alone (sort_span)
+void radix_pass_span27(SortBatch& sb, int shift, bool xform, hipStream_t s) {
+  static const int force = getenv("B3GS_SORT9_ITEMS") ? atoi(getenv("B3GS_SORT9_ITEMS")) : 0;   // (A/B switch)
+  if ((force ? force : (sb.n == 1 ? 8 : 16)) == 8) radix_pass_t<9, 8, true>(sb, shift, 9, xform, s);
+  else radix_pass_t<9, 16, true>(sb, shift, 9, xform, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1157,7 +1032,7 @@ __device__ __forceinline__ void emit_instances_body(const EmitBatch& eb, uint32_
     const uint32_t before = (lane < sub && lane < (uint32_t)eb.subs) ? job.soffs[(size_t)chunk * eb.subs + lane] : 0u;
     uint32_t base = job.chunk_base[chunk];
     if (own_sum == 0u) return;   // nothing in this sub-block (culled tail, finished tiles only)
-    base += wave_sum(before);
+    base += b3gs_wave_sum(before);
     // inclusive end of every Gaussian's instance run: offset of this 256-Gaussian sub-block (chunk base + the sums of
     // the sub-blocks before it: uniform scalar loads) + the scan inside the sub-block
     if (sub > 64u)   // (more than 64 sub-blocks per chunk: P > 2^24, not reachable through the scan's own limit)
@@ -1345,7 +1220,7 @@ __device__ __forceinline__ void scan2_chunk_apply_body(const Scan2Batch& sb, uin
     for (int r = 0; r < SCAN_ITEMS; r++) {
       const int64_t i = wb + r * 64 + lane;
       const uint32_t v = i < P ? scount[i] : 0u;
-      inc[r] = run + wave_incl_scan(v);
+      inc[r] = run + b3gs_wave_scan(v, lane);
       run = __shfl(inc[r], 63, 64);
     }
     if (lane == 0) wave_tot[w] = run;
@@ -1414,7 +1289,7 @@ struct RepairArgs {
   EmitBatch eb;
   SortBatch tb[2];          // tile-split passes (in / out already swapped for pass 1; ranges set on the last one)
   int32_t passes, bits[2];
-  uint32_t emit_blocks, max_blk;
+  uint32_t emit_blocks;
   uint32_t* barrier;        // [2] arrival counter (zeroed by scan_chunk_offsets of the same forward) | status (bit 0: time-out)
 };
 
@@ -1448,33 +1323,12 @@ __device__ __forceinline__ bool grid_barrier(uint32_t* counter, uint32_t target,
   return s_ok != 0u;
 }
 
-// one radix tile of 4096 keys counted by 256 threads (the stand-alone radix_hist counts four per 1024-thread workgroup)
-__device__ __forceinline__ void radix_hist_tile_body(const SortBatch& sb, int pass_shift, uint32_t blk, uint32_t by, uint32_t* h) {
-  const SortJob& job = sb.j[by];
-  if (blk >= job.nblk) return;
-  const int shift = pass_shift + job.shift_base;
-  const uint32_t off = job.off_ptr ? min(*job.off_ptr, job.n_cap) : 0u;
-  const uint32_t* __restrict__ keys = job.kin + off;
-  const uint32_t n = job.n_ptr ? min(*job.n_ptr, job.n_cap - off) : job.n_cap - off;
-  if ((uint64_t)blk * B3GS_SORT_TILE >= n) return;
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)blk * B3GS_SORT_TILE;
-#pragma unroll
-  for (int k = 0; k < B3GS_SORT_ITEMS; k++) {
-    const uint64_t i = base + k * B3GS_SORT_THREADS + threadIdx.x;
-    if (i < n) atomicAdd(&h[(keys[i] >> shift) & 0xFF], 1u);
-  }
-  __syncthreads();
-  job.hist[(size_t)threadIdx.x * hist_stride(job.nblk) + blk] = h[threadIdx.x];
-}
-
 template <bool HAS_VAL>
 union RepairShared {
   uint32_t tmp[8];
   uint32_t hist[256];
   EmitShared emit;
-  ScatterShared<HAS_VAL> scatter;
+  ScatterShared<8, B3GS_SORT_ITEMS, HAS_VAL> scatter;
 };
 
 template <bool HAS_VAL>
@@ -1529,29 +1383,30 @@ __global__ void __launch_bounds__(256) repair_kernel(RepairArgs ra) {
   }
   // radix tiles that hold instances of segment 2 (N2 is on the device since the second phase; the host only knows
   // the capacity): the widest view bounds the loops below
+  constexpr int ITEMS = B3GS_SORT_ITEMS;
   uint32_t used_blk = 0;
-  for (uint32_t v = 0; v < nv; v++) {
-    const SortJob& j = ra.tb[0].j[v];
-    const uint32_t off = min(*j.off_ptr, j.n_cap);
-    const uint32_t n = min(*j.n_ptr, j.n_cap - off);
-    used_blk = max(used_blk, (n + (uint32_t)B3GS_SORT_TILE - 1u) / (uint32_t)B3GS_SORT_TILE);
-  }
-  used_blk = min(used_blk, ra.max_blk);
+  for (uint32_t v = 0; v < nv; v++) used_blk = max(used_blk, sort_span<ITEMS, false>(ra.tb[0].j[v]).used);
   for (int p = 0; p < ra.passes; p++) {
     const SortBatch& tb = ra.tb[p];
     REPAIR_SYNC();
-    for (uint32_t b = wg; b < used_blk * nv; b += G) {
-      radix_hist_tile_body(tb, 8 * p, b % used_blk, b / used_blk, sh.hist);
+    for (uint32_t b = wg; b < used_blk * nv; b += G) {   // (one tile per 256 threads; the stand-alone radix_hist counts four)
+      const SortJob& job = tb.j[b / used_blk];
+      const SortSpan sp = sort_span<ITEMS, false>(job);
+      const uint32_t blk = b % used_blk;
+      if (blk < sp.used) {
+        radix_hist_tile<8, ITEMS, false>(job, sp, 8 * p, 0, blk, threadIdx.x, sh.hist);
+        job.hist[(size_t)threadIdx.x * hist_stride(job.nblk) + blk] = sh.hist[threadIdx.x];
+      }
       __syncthreads();
     }
     REPAIR_SYNC();
     for (uint32_t b = wg; b < 256u * nv; b += G) {
-      radix_rowscan_body(tb, b & 255u, b >> 8, sh.tmp);
+      radix_rowscan_body<8, ITEMS, false>(tb.j[b >> 8], b & 255u, sh.tmp);
       __syncthreads();
     }
     REPAIR_SYNC();
     for (uint32_t b = wg; b < used_blk * nv; b += G) {
-      radix_scatter_body<HAS_VAL, 8>(tb, 8 * p, b % used_blk, b / used_blk, sh.scatter);
+      radix_scatter_body<8, ITEMS, HAS_VAL, 8, false>(tb.j[b / used_blk], 8 * p, 0, b % used_blk, sh.scatter);
       __syncthreads();
     }
   }
@@ -1617,7 +1472,7 @@ void b3gs_launch_sort_u32_index(const uint32_t* keys, uint32_t* const skey[2], u
                                 uint32_t* hist, hipStream_t s) {
   SortBatch db;
   db.n = 1;
-  db.j[0] = SortJob{keys, nullptr, skey[1], sval[1], nullptr, n, b3gs_sort_blocks((int64_t)n), 0, hist, nullptr, nullptr};
+  db.j[0] = SortJob{keys, nullptr, skey[1], sval[1], nullptr, n, 0 /* nblk: radix_pass */, 0, hist, nullptr, nullptr};
   for (int pass = 0; pass < 4; pass++) {
     radix_pass(db, 8 * pass, s);
     const int dst = pass & 1;  // destination of the NEXT pass
@@ -1649,7 +1504,6 @@ void b3gs_launch_depth_order_batch(int32_t P, int nviews, const BinJob* jobs, hi
   AdoptBatch adopt;
   adopt.n = 0;
   int sorted_view[B3GS_MAX_FUSED_VIEWS];
-  const uint32_t pblk = b3gs_sort_blocks((int64_t)P);
   bool span27 = true;
   for (int v = 0; v < nviews; v++) span27 = span27 && jobs[v].key_bits == 27;
   const int npass = span27 ? 3 : 4;
@@ -1671,12 +1525,12 @@ void b3gs_launch_depth_order_batch(int32_t P, int nviews, const BinJob* jobs, hi
     if (hinted && jobs[v].hint_trusted) continue;
     sorted_view[db.n] = v;
     SortJob& sj = db.j[db.n++];
-    sj = SortJob{g.depth_key, nullptr, g.skey[first_dst], g.sval[first_dst], nullptr, (uint32_t)P, pblk, 0, g.hist,
+    sj = SortJob{g.depth_key, nullptr, g.skey[first_dst], g.sval[first_dst], nullptr, (uint32_t)P, 0 /* nblk: radix_pass */, 0, g.hist,
                  nullptr, nullptr, {flag[0], flag[1]}};
     if (hinted) sj.gate = jobs[v].hint_word;
   }
   for (int pass = 0; pass < npass; pass++) {
-    if (span27) radix9_pass(db, 9 * pass, pass == 0, s);
+    if (span27) radix_pass_span27(db, 9 * pass, pass == 0, s);
     else radix_pass(db, 8 * pass, s);
     // (not swap_in_out: the first pass reads depth_key, which no pass may overwrite)
     for (int k = 0; k < db.n; k++) {
@@ -1921,12 +1775,8 @@ void b3gs_launch_round2_batch(int32_t P, int nviews, const BinJob* jobs, hipStre
     ra.eb = eb;
     ra.passes = passes;
     ra.emit_blocks = (uint32_t)((rest + 255) / 256);
-    ra.max_blk = 0;
     bool any_val = false;
-    for (int v = 0; v < nviews; v++) {
-      ra.max_blk = tb.j[v].nblk > ra.max_blk ? tb.j[v].nblk : ra.max_blk;
-      any_val = any_val || tb.j[v].vout != nullptr;
-    }
+    for (int v = 0; v < nviews; v++) any_val = any_val || tb.j[v].vout != nullptr;
     build_tile_split(tb, rb, passes, d.tbits, 2, [&](int p, int bits) { ra.tb[p] = tb; ra.bits[p] = bits; });
     ra.barrier = jobs[0].im.header + B3GS_HDR_REPAIR_BARRIER;
     for (int v = 0; v < B3GS_MAX_FUSED_VIEWS; v++) ra.overflow[v] = v < nviews ? jobs[v].overflow_flag : nullptr;

@@ -51,6 +51,7 @@ struct AdjWs {
 // base == nullptr: only the size and the offsets are wanted; the pointers are then carved from ADJ_NO_BASE
 static char* const ADJ_NO_BASE = reinterpret_cast<char*>((uintptr_t)1 << 20);
 
+// (tests/test_gpu_sort_u32_index.py reads gkey, skey[0] and sval[0] of the build's last sort back from this layout: keep them in step)
 static size_t adj_carve(char* base, int64_t V, int64_t F, AdjWs* w) {
   if (!base) base = ADJ_NO_BASE;
   char* cur = base;
