@@ -156,6 +156,10 @@ class B3gsContribOut(C.Structure):
     _fields_ = [("weight_q32", C.c_void_p), ("hits", C.c_void_p), ("wmax_bits", C.c_void_p), ("dominant", C.c_void_p)]
 
 
+class B3gsCameraModel(C.Structure):
+    _fields_ = [("model", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_params", C.c_int32), ("params", C.c_double * 12)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -210,7 +214,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: per-pixel geometry maps
            "b3gs_blend_pixel_maps_batch",
            # added to ABI 18: weighted k-means codebooks
-           "b3gs_kmeans_workspace_bytes", "b3gs_kmeans_assign", "b3gs_kmeans")
+           "b3gs_kmeans_workspace_bytes", "b3gs_kmeans_assign", "b3gs_kmeans",
+           # added to ABI 18: undistorting a COLMAP dataset
+           "b3gs_camera_points", "b3gs_undistort_map", "b3gs_remap_batch")
 
 _lib = None
 
@@ -422,6 +428,12 @@ def lib():
     L.b3gs_kmeans_assign.restype = C.c_int
     L.b3gs_kmeans.argtypes = [I32, I32, I32, I32, V, V, V, V, V, V, V, V]
     L.b3gs_kmeans.restype = C.c_int
+    L.b3gs_camera_points.argtypes = [C.POINTER(B3gsCameraModel), I32, I64, V, V, V, V]
+    L.b3gs_camera_points.restype = C.c_int
+    L.b3gs_undistort_map.argtypes = [C.POINTER(B3gsCameraModel), I32, I32, C.c_double, C.c_double, V, V]
+    L.b3gs_undistort_map.restype = C.c_int
+    L.b3gs_remap_batch.argtypes = [I32, C.POINTER(C.c_void_p), I32, I32, I32, V, I32, I32, C.POINTER(C.c_void_p), V, V]
+    L.b3gs_remap_batch.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

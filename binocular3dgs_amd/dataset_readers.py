@@ -263,7 +263,7 @@ def _colmap_cameras(source_path: str, images: str) -> List[CameraInfo]:
             fx, fy = params[0], params[1]
         else:
             raise ValueError(f"COLMAP camera model {model} of camera {cam_id}: only undistorted datasets (SIMPLE_PINHOLE or "
-                             "PINHOLE cameras) are supported")
+                             "PINHOLE cameras) are supported.  `python -m binocular3dgs_amd.undistort -s SRC -o DST` writes one")
         path = os.path.join(source_path, images, os.path.basename(name))
         out.append(CameraInfo(uid=cam_id, R=np.transpose(quaternion_to_rotation(q)), T=np.array(t),
                               FovY=focal2fov(fy, height), FovX=focal2fov(fx, width), image_path=path,

@@ -1185,6 +1185,46 @@ int b3gs_kmeans_assign(int32_t N, int32_t D, int32_t K, const float* x, const fl
 int b3gs_kmeans(int32_t N, int32_t D, int32_t K, int32_t iters, const float* x, const float* weights, float* codebook,
                 int32_t* codes, int32_t* counts, double* distortion, void* workspace, b3gs_stream_t stream);
 
+/* ---- undistorting a COLMAP dataset (added to ABI 18; binocular3dgs_amd/undistort.py, csrc/undistort.hip) -------------
+ * Camera models with lens distortion, by COLMAP's model id and parameter order: 2 SIMPLE_RADIAL (f, cx, cy, k), 3 RADIAL
+ * (f, cx, cy, k1, k2), 4 OPENCV (fx, fy, cx, cy, k1, k2, p1, p2), 5 OPENCV_FISHEYE (fx, fy, cx, cy, k1..k4), 6 FULL_OPENCV
+ * (fx, fy, cx, cy, k1, k2, p1, p2, k3..k6), 8 SIMPLE_RADIAL_FISHEYE (f, cx, cy, k), 9 RADIAL_FISHEYE (f, cx, cy, k1, k2).
+ * Any other id, or n_params that does not belong to the id, is B3GS_ERR_ARG.  The B3gsCameraModel is host memory; every other
+ * pointer is a device pointer unless said otherwise.  Pixel coordinates have their origin at the top-left corner of the image
+ * and pixel centres at +0.5 (COLMAP's convention).  All arithmetic on coordinates is fp64; distort() on normalised coordinates
+ * is one fixed sequence of operations per model (csrc/undistort.hip states it, tests/undistort_ref.py repeats it in numpy):
+ * the same bits for the four models without a transcendental (2, 3, 4, 6).  One launch per call, no atomics, no host read;
+ * arguments are checked before the first HIP call.
+ *
+ * b3gs_camera_points: n points xy [n,2] -> out [n,2].  inverse == 0: u = (x - cx) / fx, distort, x' = fx u' + cx.
+ *   inverse != 0: the point whose distortion is xy, by Newton's iteration on (u, v) from the distorted point: the 2x2 Jacobian
+ *   from forward differences of distort() with h = 1e-6 max(1, |coordinate|), at most 50 iterations, converged when the squared
+ *   step is below 1e-22, given up when the Jacobian of an iterate has no positive determinant and trace (the iterate is
+ *   behind the fold-over of the distortion) or is not finite; converged [n] (needed when inverse != 0, else optional) receives
+ *   1 or 0.  A point that did not converge (it is not the image of a point in front of the fold-over) comes back unchanged.
+ * b3gs_undistort_map: for every pixel (i, j) of an output pinhole W x H with focal lengths fx, fy and the principal point at
+ *   (W/2, H/2): u = ((i + 0.5) - W/2) / fx, distort, x = (fx_cam u' + cx_cam) - 0.5, X = floor(x * 256 + 0.5) clamped to
+ *   [-2^30, 2^30], -2^30 when not finite; map [H,W,2] int32 = (X, Y): the source position of the output pixel's centre with
+ *   pixel centres at integers and 8 fractional bits.  map is 8-byte aligned.
+ * b3gs_remap_batch: up to 8 uint8 sources [Hs,Ws,C] of one size, C in {1, 3, 4}, through one map [H,W,2] into out[i] [H,W,C]:
+ *   x0 = X >> 8, ax = X & 255 (the same for y); the taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), each index
+ *   clamped to the image, with the weights (256 - ax | ax) * (256 - ay | ay); out = (sum w p + 32768) >> 16 per channel.
+ *   valid [H,W] uint8 = 255 where -128 <= X < 256 Ws - 128 and -128 <= Y < 256 Hs - 128 (the sample centre lies inside the
+ *   source), else 0, and there out is 0 in every channel.  src / out are HOST arrays of nviews device pointers; src[i] is
+ *   4-byte aligned.  Every output pixel owns its bytes; a wrong map gives wrong pixels, never an access outside the buffers. */
+#define B3GS_MAX_REMAP_VIEWS 8
+typedef struct B3gsCameraModel {
+  int32_t model;         /* COLMAP's model id */
+  int32_t width, height; /* the image size the parameters belong to */
+  int32_t n_params;
+  double params[12];
+} B3gsCameraModel;
+int b3gs_camera_points(const B3gsCameraModel* cam, int32_t inverse, int64_t n, const double* xy, double* out, uint8_t* converged,
+                       b3gs_stream_t stream);
+int b3gs_undistort_map(const B3gsCameraModel* cam, int32_t W, int32_t H, double fx, double fy, int32_t* map, b3gs_stream_t stream);
+int b3gs_remap_batch(int32_t nviews, const uint8_t* const* src, int32_t Hs, int32_t Ws, int32_t C, const int32_t* map, int32_t H,
+                     int32_t W, uint8_t* const* out, uint8_t* valid, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
