@@ -107,7 +107,8 @@ __global__ void __launch_bounds__(256) knn3_kernel(int P, const float* __restric
 struct KnnWs {
   float* part; uint32_t* codes; uint32_t* skey[2]; uint32_t* sval[2]; uint32_t* hist; float* sorted; Box* boxes;
 };
-// (tests/test_gpu_sort_u32_index.py reads codes, skey[0] and sval[0] back from this layout: keep them in step)
+// (tests/test_gpu_sort_u32_index.py reads codes, skey[0] and sval[0] back from this layout, tests/test_gpu_knn_edges.py
+// part, codes, sval[0], sorted and boxes -- a Box is 6 floats, lo[3] then hi[3]: keep them in step)
 size_t carve_ws(char* base, int32_t P, KnnWs* w) {
   char* cur = base;
   const size_t p = (size_t)(P > 0 ? P : 1);
