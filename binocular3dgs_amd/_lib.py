@@ -160,6 +160,17 @@ class B3gsCameraModel(C.Structure):
     _fields_ = [("model", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_params", C.c_int32), ("params", C.c_double * 12)]
 
 
+class B3gsSimilarity(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("s", C.c_double), ("ln_s", C.c_double), ("q", C.c_double * 4),
+                ("D1", C.c_double * 9), ("D2", C.c_double * 25), ("D3", C.c_double * 49)]
+
+
+class B3gsSelect(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("flags", "nviews", "min_views", "mask_h", "mask_w")]
+                + [("logit_min", C.c_float), ("log_max_scale", C.c_float), ("box", C.c_double * 12), ("half", C.c_double * 3),
+                   ("centre", C.c_double * 3), ("r2", C.c_double), ("cameras", C.c_void_p), ("masks", C.c_void_p)])
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -216,7 +227,10 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: weighted k-means codebooks
            "b3gs_kmeans_workspace_bytes", "b3gs_kmeans_assign", "b3gs_kmeans",
            # added to ABI 18: undistorting a COLMAP dataset
-           "b3gs_camera_points", "b3gs_undistort_map", "b3gs_remap_batch")
+           "b3gs_camera_points", "b3gs_undistort_map", "b3gs_remap_batch",
+           # added to ABI 18: editing a trained model
+           "b3gs_transform_points", "b3gs_transform_gaussians", "b3gs_select_gaussians", "b3gs_nearest_query_index",
+           "b3gs_similarity_sums_workspace_bytes", "b3gs_similarity_sums")
 
 _lib = None
 
@@ -434,6 +448,18 @@ def lib():
     L.b3gs_undistort_map.restype = C.c_int
     L.b3gs_remap_batch.argtypes = [I32, C.POINTER(C.c_void_p), I32, I32, I32, V, I32, I32, C.POINTER(C.c_void_p), V, V]
     L.b3gs_remap_batch.restype = C.c_int
+    L.b3gs_transform_points.argtypes = [I64, V, C.POINTER(B3gsSimilarity), V, V]
+    L.b3gs_transform_points.restype = C.c_int
+    L.b3gs_transform_gaussians.argtypes = [I32, I32, V, V, V, V, C.POINTER(B3gsSimilarity), V, V, V, V, V]
+    L.b3gs_transform_gaussians.restype = C.c_int
+    L.b3gs_select_gaussians.argtypes = [I32, V, V, V, C.POINTER(B3gsSelect), V, V, V]
+    L.b3gs_select_gaussians.restype = C.c_int
+    L.b3gs_nearest_query_index.argtypes = [I64, V, I64, F, V, V, V, V]
+    L.b3gs_nearest_query_index.restype = C.c_int
+    L.b3gs_similarity_sums_workspace_bytes.argtypes = [I64]
+    L.b3gs_similarity_sums_workspace_bytes.restype = C.c_size_t
+    L.b3gs_similarity_sums.argtypes = [I64, V, I64, V, V, V, F, V, C.POINTER(C.c_double), C.POINTER(C.c_double), V, V, V]
+    L.b3gs_similarity_sums.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -137,6 +137,22 @@ static Tensor nearest_query(const Tensor& a, const Tensor& ws, int64_t nb, doubl
   return out;
 }
 
+// -> (dist float32 [Na], index int32 [Na]): the nearest point of b as well, -1 when none lies within max_dist
+static std::tuple<Tensor, Tensor> nearest_query_index(const Tensor& a, const Tensor& ws, int64_t nb, double max_dist) {
+  Tensor q = rows3(a, at::kFloat, "a");
+  check_max_dist(max_dist);
+  const at::Device dev = q.device();
+  Tensor w = dev_input(ws, at::kByte, "workspace", kToolsDeviceOnly, &dev).contiguous();
+  if (nb < 1 || nb > INT32_MAX || (size_t)w.numel() < b3gs_nearest_workspace_bytes(nb)) throw py::value_error("nearest_distances: the workspace is too small");
+  Tensor out = at::empty({q.size(0)}, at::TensorOptions().dtype(at::kFloat).device(dev));
+  Tensor index = at::empty({q.size(0)}, at::TensorOptions().dtype(at::kInt).device(dev));
+  DeviceGuard guard(dev);
+  check(b3gs_nearest_query_index(q.size(0), ptr_or_null<float>(q), nb, (float)max_dist, w.data_ptr(), ptr_or_null<float>(out),
+                                 ptr_or_null<int32_t>(index), cur_stream(dev)),
+        "b3gs_nearest_query_index");
+  return {out, index};
+}
+
 // dist float32 [N], mask bool [N] or None -> out (float64 [3] on the device, written): sum, count, count below tau
 static void cloud_score(const Tensor& dist, const c10::optional<Tensor>& mask, double tau, Tensor out) {
   Tensor d = dev_input(dist, at::kFloat, "dist", kToolsDeviceOnly).contiguous();
@@ -164,6 +180,7 @@ void bind_meshtools(py::module_& m) {
   m.def("mesh_sample_emit", &mesh_sample_emit, py::arg("vertices"), py::arg("faces"), py::arg("spacing"), py::arg("workspace"), py::arg("npoints"));
   m.def("nearest_grid", &nearest_grid, py::arg("b"), py::arg("max_dist"));
   m.def("nearest_query", &nearest_query, py::arg("a"), py::arg("workspace"), py::arg("nb"), py::arg("max_dist"));
+  m.def("nearest_query_index", &nearest_query_index, py::arg("a"), py::arg("workspace"), py::arg("nb"), py::arg("max_dist"));
   m.def("cloud_score", &cloud_score, py::arg("dist"), py::arg("mask"), py::arg("tau"), py::arg("out"));
 }
 

@@ -490,6 +490,54 @@ __global__ void __launch_bounds__(TPB) near_query_kernel(int64_t na, const float
   out[i] = fminf(max_dist, sqrt_rn(best));
 }
 
+// The same walk, keeping the point as well: sidx[j] is the index in b of sorted[j].  Among equal d2 the smallest index wins,
+// whatever the order of the cells and of the points inside one; the strict bound test above never cuts off an equal d2.
+__global__ void __launch_bounds__(TPB) near_query_index_kernel(int64_t na, const float* __restrict__ a, const NGrid* __restrict__ gp,
+                                                               const uint2* __restrict__ cells, const float4* __restrict__ sorted,
+                                                               const uint32_t* __restrict__ sidx, float max_dist, float* __restrict__ out,
+                                                               int32_t* __restrict__ index) {
+  const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= na) return;
+  const NGrid g = *gp;
+  const float qx = a[3 * i], qy = a[3 * i + 1], qz = a[3 * i + 2];
+  const int32_t nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
+  const int32_t cx = clamp_cell(cell_coord(qx, g.o[0], g.h), -1, nx), cy = clamp_cell(cell_coord(qy, g.o[1], g.h), -1, ny),
+                cz = clamp_cell(cell_coord(qz, g.o[2], g.h), -1, nz);
+  const float md2 = max_dist * max_dist * 1.0002f;
+  float best = INFINITY;
+  uint32_t bidx = 0xFFFFFFFFu;
+  auto scan = [&](int32_t x, int32_t y, int32_t z) {
+    const uint2 r = cells[((size_t)z * ny + y) * nx + x];
+    for (uint32_t j = r.x; j < r.y; j++) {
+      const float4 p = sorted[j];
+      const float dx = __fsub_rn(qx, p.x), dy = __fsub_rn(qy, p.y), dz = __fsub_rn(qz, p.z);
+      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+      const uint32_t src = sidx[j];
+      if (d2 < best || (d2 == best && src < bidx)) best = d2, bidx = src;
+    }
+  };
+  for (int32_t s = 0; s <= g.nshell; s++) {
+    if (s >= 2) {
+      const float lb = ((float)(s - 1) - 0.00390625f) * g.h * 0.9999f;
+      if (lb * lb > fminf(best, md2)) break;
+    }
+    const int32_t z0 = max(cz - s, 0), z1 = min(cz + s, nz - 1), y0 = max(cy - s, 0), y1 = min(cy + s, ny - 1);
+    const int32_t x0 = max(cx - s, 0), x1 = min(cx + s, nx - 1);
+    for (int32_t z = z0; z <= z1; z++)
+      for (int32_t y = y0; y <= y1; y++) {
+        if (z - cz == s || cz - z == s || y - cy == s || cy - y == s) {
+          for (int32_t x = x0; x <= x1; x++) scan(x, y, z);
+        } else {
+          if (cx - s >= 0 && cx - s < nx) scan(cx - s, y, z);
+          if (s > 0 && cx + s >= 0 && cx + s < nx) scan(cx + s, y, z);
+        }
+      }
+  }
+  const float d = sqrt_rn(best);
+  out[i] = fminf(max_dist, d);
+  index[i] = (bidx != 0xFFFFFFFFu && d <= max_dist) ? (int32_t)bidx : -1;
+}
+
 // ---- the score of one direction ----------------------------------------------------------------------------------------
 constexpr int SCORE_Q = 3;            // sum of the distances, points counted, points nearer than tau
 
@@ -674,6 +722,21 @@ extern "C" int b3gs_nearest_query(int64_t Na, const float* a, int64_t Nb, float 
   near_carve(static_cast<char*>(const_cast<void*>(workspace)), Nb, &w);
   hipLaunchKernelGGL(near_query_kernel, dim3(blocks_of(Na)), dim3(TPB), 0, (hipStream_t)stream, Na, a, (const NGrid*)w.grid,
                      (const uint2*)w.cells, (const float4*)w.sorted, max_dist, out);
+  return b3gs_launch_status(what);
+}
+
+extern "C" int b3gs_nearest_query_index(int64_t Na, const float* a, int64_t Nb, float max_dist, const void* workspace, float* out,
+                                        int32_t* index, b3gs_stream_t stream) {
+  static const char* what = "b3gs_nearest_query_index";
+  if (Na < 0 || Na > INT32_MAX || Nb < 1 || Nb > INT32_MAX) return b3gs_fail(B3GS_ERR_ARG, what, "0 <= Na <= 2^31 - 1, 1 <= Nb <= 2^31 - 1");
+  if (!(max_dist > 0.0f) || !(max_dist <= FLT_MAX)) return b3gs_fail(B3GS_ERR_ARG, what, "max_dist is positive and finite");
+  if (!aligned256(workspace)) return b3gs_fail(B3GS_ERR_ARG, what, "a 256-byte aligned workspace is needed");
+  if (Na == 0) return B3GS_OK;
+  if (!a || !out || !index) return b3gs_fail(B3GS_ERR_ARG, what, "NULL pointer");
+  NearWs w;
+  near_carve(static_cast<char*>(const_cast<void*>(workspace)), Nb, &w);
+  hipLaunchKernelGGL(near_query_index_kernel, dim3(blocks_of(Na)), dim3(TPB), 0, (hipStream_t)stream, Na, a, (const NGrid*)w.grid,
+                     (const uint2*)w.cells, (const float4*)w.sorted, (const uint32_t*)w.sval[0], max_dist, out, index);
   return b3gs_launch_status(what);
 }
 

@@ -115,6 +115,12 @@ class NearestGrid:
         from . import _C
         return _C.nearest_query(a, self._ws, self.nb, self.max_dist)
 
+    def query_index(self, a: torch.Tensor):
+        """-> (distances float32 [Na], index int32 [Na]): the nearest point of `b` as well, among equal squared distances the
+        smallest index, -1 where nothing lies within max_dist (edit.register pairs points with it)."""
+        from . import _C
+        return _C.nearest_query_index(a, self._ws, self.nb, self.max_dist)
+
     def params(self) -> dict:
         head = self._ws[:32].cpu()
         f, i = head.view(torch.float32), head.view(torch.int32)

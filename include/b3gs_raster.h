@@ -762,6 +762,10 @@ int b3gs_mesh_emit(const B3gsTsdfVolume* volume, void* workspace, int64_t nverts
  * and stops at the first shell that provably holds nothing nearer than the best so far or max_dist (csrc/meshtools.hip states
  * the bound); at most `shells` <= 17 shells.  max_dist > 0 and finite; the coordinates are finite.
  *
+ * b3gs_nearest_query_index (added for binocular3dgs_amd/edit.py: register): the same walk over the same workspace; besides
+ * out it writes index [Na] int32, the index into b of the nearest point, among equal float32 d2 the smallest index, and -1
+ * when sqrt(min_j d2) > max_dist (nothing lies within max_dist; out is max_dist there).
+ *
  * b3gs_cloud_score: out[0] = the fp64 sum of dist[i] over the points with mask[i] != 0 (mask NULL: all), out[1] = their
  * number, out[2] = the number of them with dist[i] < tau.  Per-workgroup fp64 partials, folded in index order by one wave:
  * the same bits on every call. */
@@ -782,6 +786,8 @@ size_t b3gs_nearest_workspace_bytes(int64_t Nb);
 int b3gs_nearest_grid(int64_t Nb, const float* b, float max_dist, void* workspace, b3gs_stream_t stream);
 int b3gs_nearest_query(int64_t Na, const float* a, int64_t Nb, float max_dist, const void* workspace, float* out,
                        b3gs_stream_t stream);
+int b3gs_nearest_query_index(int64_t Na, const float* a, int64_t Nb, float max_dist, const void* workspace, float* out,
+                             int32_t* index, b3gs_stream_t stream);
 size_t b3gs_cloud_score_workspace_bytes(int64_t N);
 int b3gs_cloud_score(int64_t N, const float* dist, const uint8_t* mask, float tau, double* out, void* workspace,
                      b3gs_stream_t stream);
@@ -1224,6 +1230,75 @@ int b3gs_camera_points(const B3gsCameraModel* cam, int32_t inverse, int64_t n, c
 int b3gs_undistort_map(const B3gsCameraModel* cam, int32_t W, int32_t H, double fx, double fy, int32_t* map, b3gs_stream_t stream);
 int b3gs_remap_batch(int32_t nviews, const uint8_t* const* src, int32_t Hs, int32_t Ws, int32_t C, const int32_t* map, int32_t H,
                      int32_t W, uint8_t* const* out, uint8_t* valid, b3gs_stream_t stream);
+
+/* ---- editing a trained model (added to ABI 18; binocular3dgs_amd/edit.py, csrc/edit.hip) ----
+ * A similarity is x' = s R x + t, s > 0, R a proper rotation.  B3gsSimilarity is HOST memory, all doubles: R row-major, t, s,
+ * ln_s = log(s), q = the unit quaternion of R as (w, x, y, z), and the rotation matrices D1 [3x3], D2 [5x5], D3 [7x7]
+ * (row-major) of the real spherical harmonics of bands 1..3 in the basis and sign convention of csrc/preprocess.hip:
+ * Y_l(d)^T D_l = Y_l(R^T d)^T for every unit d (binocular3dgs_amd/edit.py: sh_rotation_matrices).  The library trusts the
+ * caller that these belong together; it checks that every entry is finite and s > 0.
+ * Every statement below is fp64 in the operation order written, products and sums rounded one by one (no fused multiply-add),
+ * float32 inputs widened exactly, ONE rounding to float32 at the store: tests/edit_ref.py repeats it in numpy, same bits.
+ *
+ * b3gs_transform_points: out_i = s * ((R_i0 x + R_i1 y) + R_i2 z) + t_i for N points [N,3]; out may be in.
+ * b3gs_transform_gaussians: P Gaussians, raw parameters, features_rest [P, (sh_degree+1)^2 - 1, 3], sh_degree 0..3
+ *   (sh_degree 0: both features_rest pointers are ignored):
+ *     xyz'       as b3gs_transform_points
+ *     rotation'  = q (x) rotation, the Hamilton product in (w, x, y, z) order on the raw, un-normalised parameter r:
+ *                  w' = ((qw rw - qx rx) - qy ry) - qz rz      x' = ((qw rx + qx rw) + qy rz) - qz ry
+ *                  y' = ((qw ry - qx rz) + qy rw) + qz rx      z' = ((qw rz + qx ry) - qy rx) + qz rw     (the norm is kept)
+ *     scaling'   = scaling + ln_s, on the raw log parameter
+ *     features_rest'[band l, m, c] = (..((D_l[m][0] f[0] + D_l[m][1] f[1]) + D_l[m][2] f[2]) + ..), f[k] = features_rest[band l, k, c]
+ *   features_dc and opacity do not change and are not arguments.  Every Gaussian owns its output rows and a workgroup reads
+ *   its rows before it writes them: each out_* may be its input.  No atomics, no host read; P = 0 is a no-op.
+ *   Under the identity similarity every finite value keeps its bits, except that a -0.0 may come back as +0.0 (x + 0.0 and
+ *   0.0 * y + x are +0.0 for x = -0.0); a row of zeros stays a row of zeros.  Non-finite values propagate as IEEE has them.
+ * b3gs_select_gaussians: keep[i] = 1 when Gaussian i passes every test enabled in flags, else 0; seen[i] = the number of views
+ *   that see it (0 when B3GS_SELECT_VIEWS is off).  A disabled test reads nothing (its pointers may be NULL).
+ *     BOX      p_k = ((M_k0 x + M_k1 y) + M_k2 z) + M_k3 with box = M [3x4] row-major world-to-box; |p_k| <= half[k] for k = 0..2
+ *     SPHERE   d = x - centre; (dx dx + dy dy) + dz dz <= r2
+ *     OPACITY  opacity_raw >= logit_min            (a float32 compare on the raw parameter: no transcendental on the device)
+ *     SCALE    max_k scaling_raw[k] <= log_max_scale   (float32)
+ *     VIEWS    cameras: DEVICE doubles [nviews][19] = [3x4 world-to-view row-major | fx fy cx cy W H near], nviews <= 64.  A view
+ *              sees the Gaussian when, with (X, Y, Z) = the rows applied as in BOX, Z > near, u = (fx X) / Z + cx has
+ *              0 <= u < W, v = (fy Y) / Z + cy has 0 <= v < H and, when masks (DEVICE uint8 [nviews][mask_h][mask_w]) is not
+ *              NULL, masks[view][floor(v)][floor(u)] != 0 (a texel outside the plane, when W > mask_w or H > mask_h, counts
+ *              as 0).  Kept when seen >= min_views.
+ *   A Gaussian with a non-finite coordinate fails BOX, SPHERE and every view.  No atomics, no host read; P = 0 is a no-op.
+ * b3gs_similarity_sums: over the pairs i < N with 0 <= index[i] < Nb, dist[i] <= gate (float32) and mask[i] != 0 (mask NULL:
+ *   all), with a~ = a_i - origin_a and b~ = b[index[i]] - origin_b in fp64, out[18] = {n, sum a~ (3), sum b~ (3),
+ *   sum ((a~x a~x + a~y a~y) + a~z a~z), sum b~ a~^T (9, row-major: b~_r a~_c), sum ((b~x b~x + b~y b~y) + b~z b~z)}.  The
+ *   18th sum is what the residual of a similarity fit needs besides the other 17 (var b): one launch gives the fit AND its rms.  origin_a / origin_b are HOST doubles [3].
+ *   Thread t of workgroup g (256 threads, nb = clamp(ceil(N / 2048), 1, 256) workgroups) adds i = 256 g + t, + 256 nb, .. in
+ *   order; the per-workgroup partials and their fold by one wave are those of b3gs_cloud_score: the same bits on every call.
+ *   No floating-point atomic.  workspace: b3gs_similarity_sums_workspace_bytes(N) bytes, no initial content. */
+#define B3GS_SELECT_BOX 1
+#define B3GS_SELECT_SPHERE 2
+#define B3GS_SELECT_OPACITY 4
+#define B3GS_SELECT_SCALE 8
+#define B3GS_SELECT_VIEWS 16
+#define B3GS_MAX_SELECT_VIEWS 64
+typedef struct B3gsSimilarity {
+  double R[9], t[3], s, ln_s, q[4], D1[9], D2[25], D3[49];
+} B3gsSimilarity;
+typedef struct B3gsSelect {
+  int32_t flags;       /* B3GS_SELECT_* */
+  int32_t nviews, min_views, mask_h, mask_w;
+  float logit_min, log_max_scale;
+  double box[12], half[3], centre[3], r2;
+  const double* cameras;
+  const uint8_t* masks;
+} B3gsSelect;
+int b3gs_transform_points(int64_t N, const float* in, const B3gsSimilarity* xf, float* out, b3gs_stream_t stream);
+int b3gs_transform_gaussians(int32_t P, int32_t sh_degree, const float* xyz, const float* rotation, const float* scaling,
+                             const float* features_rest, const B3gsSimilarity* xf, float* out_xyz, float* out_rotation,
+                             float* out_scaling, float* out_features_rest, b3gs_stream_t stream);
+int b3gs_select_gaussians(int32_t P, const float* xyz, const float* opacity_raw, const float* scaling_raw, const B3gsSelect* sel,
+                          uint8_t* keep, int32_t* seen, b3gs_stream_t stream);
+size_t b3gs_similarity_sums_workspace_bytes(int64_t N);
+int b3gs_similarity_sums(int64_t N, const float* a, int64_t Nb, const float* b, const int32_t* index, const float* dist, float gate,
+                         const uint8_t* mask, const double* origin_a, const double* origin_b, double* out, void* workspace,
+                         b3gs_stream_t stream);
 
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
