@@ -230,7 +230,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_camera_points", "b3gs_undistort_map", "b3gs_remap_batch",
            # added to ABI 18: editing a trained model
            "b3gs_transform_points", "b3gs_transform_gaussians", "b3gs_select_gaussians", "b3gs_nearest_query_index",
-           "b3gs_similarity_sums_workspace_bytes", "b3gs_similarity_sums")
+           "b3gs_similarity_sums_workspace_bytes", "b3gs_similarity_sums",
+           # added to ABI 18: the camera pose gradient
+           "b3gs_pose_gradient_workspace_bytes", "b3gs_pose_gradient")
 
 _lib = None
 
@@ -460,6 +462,11 @@ def lib():
     L.b3gs_similarity_sums_workspace_bytes.restype = C.c_size_t
     L.b3gs_similarity_sums.argtypes = [I64, V, I64, V, V, V, F, V, C.POINTER(C.c_double), C.POINTER(C.c_double), V, V, V]
     L.b3gs_similarity_sums.restype = C.c_int
+    L.b3gs_pose_gradient_workspace_bytes.argtypes = [I32, I32]
+    L.b3gs_pose_gradient_workspace_bytes.restype = C.c_size_t
+    L.b3gs_pose_gradient.argtypes = [I32, I32, I32, V, V, V, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_double), V, V, V]
+    L.b3gs_pose_gradient.restype = C.c_int
     L.b3gs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.b3gs_mark_visible.restype = C.c_int
     L.b3gs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -65,4 +65,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_kmeans(m);
   b3::bind_undistort(m);
   b3::bind_edit(m);
+  b3::bind_pose(m);
 }

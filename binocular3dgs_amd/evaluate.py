@@ -25,8 +25,11 @@ downloads; nothing is fetched here) it is computed on the device from the same c
 (csrc/lpips.hip).  Without weights the results are what they were.
 
 python -m binocular3dgs_amd.evaluate -m MODEL_PATH [-s SOURCE] [--iteration N] [--mode png|report]
-                                     [--lpips_vgg F --lpips_lin F | --lpips_npz F]
+                                     [--lpips_vgg F --lpips_lin F | --lpips_npz F] [--align_poses N [--align_scales 4 2 1]]
 evaluates the test cameras of the dataset folder and writes results.json / per_view.json under method ours_<iteration>.
+--align_poses N: every held-out camera is first aligned to the model by N photometric steps on its pose against its own ground
+truth (pose.refine_pose: a model trained on three views lives in a frame slightly off the held-out poses); the files gain
+SSIM_aligned / PSNR_aligned / LPIPS_aligned beside the unaligned keys, per_view.json each view's twist.
 """
 from __future__ import annotations
 
@@ -220,17 +223,24 @@ def training_report(model, test_cameras, train_cameras, bg: torch.Tensor, *, bat
 
 
 # ---- results.json / per_view.json (metrics.py:105-122) ----------------------------------------------------------------
-def write_results(model_path: str, method: str, per_view: Sequence[dict], names: Sequence[str]) -> dict:
+def write_results(model_path: str, method: str, per_view: Sequence[dict], names: Sequence[str], aligned: Optional[Sequence[dict]] = None,
+                  twists=None) -> dict:
     """Writes <model_path>/results.json {method: {"SSIM", "PSNR"}} and per_view.json {method: {"SSIM": {name: v}, "PSNR":
     {name: v}}} in the reference's layout (json.dump, indent=True); the "LPIPS" key is written in both files, as
     metrics.py:112-117 does, when EVERY per-view entry carries it, and left out otherwise.  Means are fp32, as
-    torch.tensor(values).mean() is there.  Returns the two dicts."""
-    if len(per_view) != len(names):
+    torch.tensor(values).mean() is there.  `aligned` (the per-view metrics after pose alignment) adds the same keys with the
+    suffix _aligned behind them, `twists` ([n,6]) adds per_view.json's "twist": {name: [omega, t]}; without them the files are
+    what they were.  Returns the two dicts."""
+    if len(per_view) != len(names) or (aligned is not None and len(aligned) != len(names)):
         raise ValueError("one name per view")
     keys = ("SSIM", "PSNR") + (("LPIPS",) if per_view and all("LPIPS" in v for v in per_view) else ())
     vals = {k: torch.tensor([float(v[k]) for v in per_view]) for k in keys}
-    full = {method: {k: vals[k].mean().item() for k in keys}}
-    per = {method: {k: {name: x for x, name in zip(vals[k].tolist(), names)} for k in keys}}
+    if aligned is not None:
+        vals.update({k + "_aligned": torch.tensor([float(v[k]) for v in aligned]) for k in keys})
+    full = {method: {k: vals[k].mean().item() for k in vals}}
+    per = {method: {k: {name: x for x, name in zip(vals[k].tolist(), names)} for k in vals}}
+    if twists is not None:
+        per[method]["twist"] = {name: [float(x) for x in t] for t, name in zip(twists, names)}
     os.makedirs(model_path, exist_ok=True)
     with open(os.path.join(model_path, "results.json"), "w") as fp:
         json.dump(full, fp, indent=True)
@@ -241,10 +251,12 @@ def write_results(model_path: str, method: str, per_view: Sequence[dict], names:
 
 # ---- command line: metrics.py over the test cameras of a trained model ------------------------------------------------
 def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1, mode: str = "png", lpips_weights=None,
-        masks=None) -> dict:
+        masks=None, align_poses: int = 0, align_scales: Sequence[int] = (4, 2, 1)) -> dict:
     """Loads <model_path>/point_cloud/iteration_<it> and the dataset's test cameras (cfg_args gives the defaults, as in
     spiral.py), evaluates them, prints the means in metrics.py:107-109's format and writes results.json / per_view.json under
-    method ours_<it>.  `masks`: DTU IDR object masks per test camera (the command line does not read them)."""
+    method ours_<it>.  `masks`: DTU IDR object masks per test camera (the command line does not read them).
+    align_poses = N > 0: the cameras are refined for N iterations each (pose.refine_poses, coarse to fine over align_scales)
+    and evaluated again; the result gains "aligned" (evaluate_views of the refined cameras) and "twists"."""
     from .gaussian_model import GaussianModel
     from .scene import Scene
     from .spiral import max_iteration, read_cfg_args
@@ -271,6 +283,18 @@ def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1,
         print("  LPIPS: {:>12.7f}".format(res["LPIPS"]))
     print("")
     names = ["{0:05d}.png".format(i) for i in range(len(cams))]      # render.py:34: the file names metrics.py lists
+    if align_poses > 0:
+        from .pose import refine_poses
+        refined, twists, _ = refine_poses(model, cams, masks=masks, iters=int(align_poses), scales=tuple(align_scales), bg=bg)
+        res["aligned"] = evaluate_views(model, refined, bg, masks=masks, mode=mode, lpips_weights=lpips_weights)
+        res["twists"] = twists
+        print("  SSIM (aligned): {:>12.7f}".format(res["aligned"]["SSIM"]))
+        print("  PSNR (aligned): {:>12.7f}".format(res["aligned"]["PSNR"]))
+        if "LPIPS" in res["aligned"]:
+            print("  LPIPS (aligned): {:>12.7f}".format(res["aligned"]["LPIPS"]))
+        print("")
+        write_results(model_path, "ours_{}".format(it), res["per_view"], names, res["aligned"]["per_view"], twists)
+        return res
     write_results(model_path, "ours_{}".format(it), res["per_view"], names)
     return res
 
@@ -285,6 +309,9 @@ def main(argv=None) -> int:
     p.add_argument("--lpips_vgg", default=None, help="torchvision's vgg16-397923af.pth (a file; nothing is fetched)")
     p.add_argument("--lpips_lin", default=None, help="the LPIPS package's weights/v0.1/vgg.pth")
     p.add_argument("--lpips_npz", default=None, help="the two files converted once by lpips.save_weights")
+    p.add_argument("--align_poses", type=int, default=0, metavar="N",
+                   help="align every held-out camera to the model by N photometric pose steps before scoring it again")
+    p.add_argument("--align_scales", type=int, nargs="+", default=[4, 2, 1], help="the coarse-to-fine pyramid of the alignment")
     a = p.parse_args(argv)
     w = None
     if a.lpips_npz:
@@ -297,7 +324,7 @@ def main(argv=None) -> int:
             p.error("--lpips_vgg and --lpips_lin go together")
         from .lpips import load_weights
         w = load_weights(a.lpips_vgg, a.lpips_lin)
-    run(a.model_path, a.source_path, a.iteration, a.mode, w)
+    run(a.model_path, a.source_path, a.iteration, a.mode, w, align_poses=a.align_poses, align_scales=a.align_scales)
     return 0
 
 

@@ -1300,6 +1300,43 @@ int b3gs_similarity_sums(int64_t N, const float* a, int64_t Nb, const float* b, 
                          const uint8_t* mask, const double* origin_a, const double* origin_b, double* out, void* workspace,
                          b3gs_stream_t stream);
 
+/* ---- the camera pose gradient from the per-Gaussian gradients (added to ABI 18; csrc/pose.hip) ----
+ * A render from a moved camera is the render of the inversely moved scene, so the gradient of a loss with respect to a rigid
+ * motion is a linear reduction of the gradients the backward already wrote.  For each of nviews <= 8 views (one launch, all
+ * views share the parameters), with mu = xyz, q = rotation (raw, (w, x, y, z)), f = features_rest [P, (sh_degree+1)^2 - 1, 3]
+ * and g_mu, g_q, g_f their gradients for that view, over the rows i < P with skip[view][i] == 0 (skip NULL, or skip[view] NULL:
+ * all rows; a skipped row is not read):
+ *   out[view] = {tau_x, tau_y, tau_z, f_x, f_y, f_z}: the gradient with respect to a world-frame twist (omega, t) of the SCENE
+ *   about `pivot` c (x -> c + exp(omega) (x - c) + t); the camera's gradient is its negative.  Per row, fp64 in the operation
+ *   order written, products and sums rounded one by one (no fused multiply-add), float32 inputs widened exactly:
+ *     d = mu - c
+ *     cross_x = d_y g_z - d_z g_y      cross_y = d_z g_x - d_x g_z      cross_z = d_x g_y - d_y g_x            (g = g_mu)
+ *     h_x = ((g_x q_w - g_w q_x) + g_z q_y) - g_y q_z       = <g_q, e_x (x) q>, the Hamilton product with the pure unit e_x
+ *     h_y = ((g_y q_w - g_w q_y) + g_x q_z) - g_z q_x       h_z = ((g_z q_w - g_w q_z) + g_y q_x) - g_x q_y    (g = g_q)
+ *     s_x = s_y = s_z = 0; for band l = 1 .. sh_degree, for channel c = 0, 1, 2, with f[k] = f[band l, k, c], g[k] likewise
+ *     of g_f, each statement "s, a, j, m" below in order is  s = s + a * (g[j] * f[m] - g[m] * f[j])  (the entry G_l[j][m] = a
+ *     of the antisymmetric generator of the band rotation about that axis, d/dtheta D_l(exp(theta e_k)) at 0, and its mirror):
+ *       band 1:  s_x 1 0 1;  s_y 1 1 2;  s_z 1 0 2
+ *       band 2:  s_x 1 0 3;  s_x r3 1 2;  s_x 1 1 4;  s_y -1 0 1;  s_y r3 2 3;  s_y 1 3 4;  s_z 2 0 4;  s_z 1 1 3
+ *       band 3:  s_x r6/2 0 5;  s_x r10/2 1 4;  s_x r6/2 1 6;  s_x r6 2 3;  s_x r10/2 2 5;  s_y -r6/2 0 1;  s_y -r10/2 1 2;
+ *                s_y r6 3 4;  s_y r10/2 4 5;  s_y r6/2 5 6;  s_z 3 0 6;  s_z 2 1 5;  s_z 1 2 4
+ *       r3 = 1.7320508075688772, r6 = 2.4494897427831779, r6/2 = 1.2247448713915890, r10/2 = 1.5811388300841898
+ *     tau_k += (cross_k + 0.5 * h_k) + s_k          f_k += g_mu_k
+ *   Thread t of workgroup g (256 threads, nb = clamp(ceil(P / 1024), 1, 1024) workgroups per view) adds the rows i = 256 g + t,
+ *   + 256 nb, .. in order, each of the six sums starting from +0; the per-workgroup partials and their fold by one wave are
+ *   those of b3gs_similarity_sums: the same bits on every call.  No floating-point atomic, no host read.
+ *   sh_degree 0 reads neither features_rest pointer.  P = 0 writes zeros (no pointer but pivot and out is read).  Non-finite
+ *   inputs propagate as IEEE has them.  B3GS_ERR_ARG before the first HIP call: nviews outside 1 .. 8, sh_degree outside
+ *   0 .. 3, P < 0, a non-finite pivot, a NULL required pointer.
+ *   grad_xyz / grad_rotation / grad_features_rest / skip are HOST arrays of nviews DEVICE pointers, pivot is HOST double[3], out
+ *   is DEVICE double[nviews][6]; workspace: b3gs_pose_gradient_workspace_bytes(P, nviews) bytes, no initial content. */
+#define B3GS_MAX_POSE_VIEWS 8
+size_t b3gs_pose_gradient_workspace_bytes(int32_t P, int32_t nviews);
+int b3gs_pose_gradient(int32_t P, int32_t sh_degree, int32_t nviews, const float* xyz, const float* rotation,
+                       const float* features_rest, const float* const* grad_xyz, const float* const* grad_rotation,
+                       const float* const* grad_features_rest, const uint8_t* const* skip, const double* pivot, double* out,
+                       void* workspace, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
