@@ -1168,6 +1168,54 @@ typedef struct B3gsPixelMapView {
 } B3gsPixelMapView;
 int b3gs_blend_pixel_maps_batch(int32_t nviews, const B3gsPixelMapView* views, b3gs_stream_t stream);
 
+/* ---- segmentation from 2D label planes (added to ABI 18; binocular3dgs_amd/segment.py, csrc/segment.hip) ----------
+ * Two more reductions of the same second walk of a finished forward's tile lists (above: positions below the pixel's
+ * n_contrib, T restarted from 1, an entry blended exactly where the forward blended it, w = alpha * T with T the
+ * transmittance in front of the entry).  Labels are bytes 0 .. nlabels - 1, 1 <= nlabels <= B3GS_MAX_LABELS; a byte
+ * >= nlabels means "no label" (255 is the conventional spelling).
+ *
+ * b3gs_label_votes_batch: every pixel gives the weight it received from a Gaussian to the label the pixel carries.
+ *   labels     per view, [H*W] bytes, required.  A pixel whose byte is >= nlabels is not walked; pixels outside W x H never count.
+ *   votes_q32  uint64 [P * nlabels], row-major [P][nlabels], shared by all views of the call and ACCUMULATED INTO (the caller
+ *              zeroes it).  votes_q32[g][l] = the sum of rint(w * 2^32) over the blended (view, pixel, entry) of Gaussian g at
+ *              the pixels labelled l -- the weight_q32 of b3gs_blend_contribution_batch under pixel_mask = (labels == l), the
+ *              same bits, for every l in one walk.  The product is exact in float32; the conversion rounds to nearest, ties to
+ *              even; 64-bit integer adds.  votes = votes_q32 / 2^32.
+ *   Nothing but integer adds reaches memory: the bits do not depend on the order of waves, tiles, views or calls.
+ *
+ * b3gs_label_render_batch: the inverse direction, a label map of per-Gaussian labels.
+ *   gaussian_label  [P] bytes, shared by all views.  A Gaussian whose byte is >= nlabels adds to no sum.
+ *   For each label l, S_l = the float32 sum, in list order, of w over the pixel's blended entries whose Gaussian carries l
+ *   (S_l = S_l + w, one rounding per entry).  Two planes of [H*W] per view, both required:
+ *   label   uint8    the smallest l that holds the largest S_l when that S_l > 0, otherwise 255
+ *   weight  float32  that S_l, or 0
+ *   Pixels that walk nothing (n_contrib == 0) get 255 and 0; every pixel inside W x H is written, the planes need no initial
+ *   content.  No atomics and no reduction across pixels: a view's planes are the same bits alone and at any position of a batch.
+ *
+ * Both calls read geometry / binning / image and write only their outputs; neither reads anything back to the host.  All
+ * views share P (P == 0: nothing is done), sizes may differ.  1..8 views per call; arguments are checked before the first
+ * HIP call (B3GS_ERR_ARG). */
+#define B3GS_MAX_LABELS 16
+typedef struct B3gsLabelVoteView {
+  const B3gsScene* view;         /* P, W, H are read */
+  const char* geometry;          /* as left by b3gs_forward_raw[_batch] + the blend forward of this view */
+  const char* binning;
+  const char* image;
+  const uint8_t* labels;         /* [H*W], the label of every pixel; a byte >= nlabels: the pixel votes for nothing */
+} B3gsLabelVoteView;
+typedef struct B3gsLabelRenderView {
+  const B3gsScene* view;         /* P, W, H are read */
+  const char* geometry;
+  const char* binning;
+  const char* image;
+  uint8_t* label;                /* [H*W] out */
+  float* weight;                 /* [H*W] out */
+} B3gsLabelRenderView;
+int b3gs_label_votes_batch(int32_t nviews, const B3gsLabelVoteView* views, int32_t nlabels, uint64_t* votes_q32,
+                           b3gs_stream_t stream);
+int b3gs_label_render_batch(int32_t nviews, const B3gsLabelRenderView* views, int32_t nlabels, const uint8_t* gaussian_label,
+                            b3gs_stream_t stream);
+
 /* ---- weighted k-means codebooks (added to ABI 18; binocular3dgs_amd/compress.py, csrc/kmeans.hip) ---------------
  * Lloyd's algorithm over N rows x [N,D] (float32) with K codes [K,D] and optional row weights w [N] (float32, not negative;
  * NULL = 1), entirely on the stream: no host read.  1 <= D <= 64, 1 <= K <= 65536, N >= 0 (N == 0: returns B3GS_OK and does
