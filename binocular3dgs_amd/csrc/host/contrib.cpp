@@ -1,8 +1,6 @@
 // Per-Gaussian render contribution (binocular3dgs_amd/importance.py): launch assembly of b3gs_blend_contribution_batch over
 // the state buffers a FusedRasterizer forward left in its slots.  No autograd: the statistics are not differentiable.
-#include "common.h"
-
-#include <vector>
+#include "walk_state.h"
 
 namespace py = pybind11;
 using at::Tensor;
@@ -34,25 +32,13 @@ static void blend_contribution(const py::list& views, Tensor weight_q32, Tensor 
   for (size_t k = 0; k < n; ++k) {
     py::tuple t = views[k].cast<py::tuple>();
     if (t.size() != 6) throw py::value_error("blend_contribution: a view is (geometry, binning, image, W, H, mask | None)");
-    Tensor geom = dev_input(t[0].cast<Tensor>(), at::kByte, "geometry", NO_CPU_C, &dev);
-    Tensor binning = dev_input(t[1].cast<Tensor>(), at::kByte, "binning", NO_CPU_C, &dev);
-    Tensor img = dev_input(t[2].cast<Tensor>(), at::kByte, "image", NO_CPU_C, &dev);
-    const int64_t W = t[3].cast<int64_t>(), H = t[4].cast<int64_t>();
-    if (W <= 0 || H <= 0) throw py::value_error("blend_contribution: W and H must be positive");
-    if (geom.numel() < (int64_t)b3gs_geometry_bytes((int32_t)P) || img.numel() < (int64_t)b3gs_image_bytes((int32_t)W, (int32_t)H))
-      throw py::value_error("blend_contribution: a state buffer is smaller than its P / W x H ask for");
-    for (const Tensor& x : {geom, binning, img}) keep.push_back(x);
-    sc[k] = B3gsScene{};
-    sc[k].P = (int32_t)P, sc[k].W = (int32_t)W, sc[k].H = (int32_t)H;
-    cv[k] = B3gsContribView{};
-    cv[k].view = &sc[k];
-    cv[k].geometry = (const char*)geom.data_ptr(), cv[k].binning = (const char*)binning.data_ptr();
-    cv[k].image = (const char*)img.data_ptr();
+    const ViewState s = view_state(t, 3, P, &dev, keep, sc[k], "blend_contribution", NO_CPU_C);
+    cv[k] = B3gsContribView{&sc[k], s.geometry, s.binning, s.image, nullptr};
     if (!t[5].is_none()) {
       Tensor m = t[5].cast<Tensor>();
       if (!m.defined() || !m.is_cuda()) raise(std::string("mask is on ") + (m.defined() ? m.device().str() : "no device") + ": " + NO_CPU_C);
       if (m.scalar_type() != at::kByte && m.scalar_type() != at::kBool) throw py::value_error("blend_contribution: a mask is uint8 or bool");
-      if (m.numel() != W * H) throw py::value_error("blend_contribution: a mask holds H * W elements");
+      if (m.numel() != s.W * s.H) throw py::value_error("blend_contribution: a mask holds H * W elements");
       m = m.contiguous();
       keep.push_back(m);
       cv[k].pixel_mask = (const uint8_t*)m.data_ptr();

@@ -1,8 +1,6 @@
 // Per-pixel geometry maps (binocular3dgs_amd/pixel_maps.py): launch assembly of b3gs_blend_pixel_maps_batch over the state
 // buffers a FusedRasterizer forward left in its slots.  No autograd: there is no backward through the maps.
-#include "common.h"
-
-#include <vector>
+#include "walk_state.h"
 
 namespace py = pybind11;
 using at::Tensor;
@@ -28,31 +26,21 @@ static void blend_pixel_maps(const py::list& views, const py::list& outs) {
   for (size_t k = 0; k < n; ++k) {
     py::tuple t = views[k].cast<py::tuple>();
     if (t.size() != 6) throw py::value_error("blend_pixel_maps: a view is (geometry, binning, image, P, W, H)");
-    Tensor geom = dev_input(t[0].cast<Tensor>(), at::kByte, "geometry", NO_CPU_P, k ? &dev : nullptr);
-    if (k == 0) dev = geom.device();
-    Tensor binning = dev_input(t[1].cast<Tensor>(), at::kByte, "binning", NO_CPU_P, &dev);
-    Tensor img = dev_input(t[2].cast<Tensor>(), at::kByte, "image", NO_CPU_P, &dev);
-    const int64_t P = t[3].cast<int64_t>(), W = t[4].cast<int64_t>(), H = t[5].cast<int64_t>();
-    if (W <= 0 || H <= 0 || W > INT32_MAX || H > INT32_MAX) throw py::value_error("blend_pixel_maps: W and H must be positive");
+    const int64_t P = t[3].cast<int64_t>();
     if (P < 0 || P > INT32_MAX) throw py::value_error("blend_pixel_maps: P is the number of Gaussians");
     if (k == 0) P0 = P;
     if (P != P0) throw py::value_error("blend_pixel_maps: the views of one call share P");
-    if (geom.numel() < (int64_t)b3gs_geometry_bytes((int32_t)P) || img.numel() < (int64_t)b3gs_image_bytes((int32_t)W, (int32_t)H))
-      throw py::value_error("blend_pixel_maps: a state buffer is smaller than its P / W x H ask for");
-    for (const Tensor& x : {geom, binning, img}) keep.push_back(x);
-    sc[k] = B3gsScene{};
-    sc[k].P = (int32_t)P, sc[k].W = (int32_t)W, sc[k].H = (int32_t)H;
+    const ViewState s = view_state(t, 4, P, k ? &dev : nullptr, keep, sc[k], "blend_pixel_maps", NO_CPU_P);
+    dev = s.dev;
     pv[k] = B3gsPixelMapView{};
-    pv[k].view = &sc[k];
-    pv[k].geometry = (const char*)geom.data_ptr(), pv[k].binning = (const char*)binning.data_ptr();
-    pv[k].image = (const char*)img.data_ptr();
+    pv[k].view = &sc[k], pv[k].geometry = s.geometry, pv[k].binning = s.binning, pv[k].image = s.image;
     py::tuple o = outs[k].cast<py::tuple>();
     if (o.size() != 5) throw py::value_error("blend_pixel_maps: the planes of a view are (median_depth, depth_m1, depth_m2, dominant, count)");
     void* ptr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int j = 0; j < 5; ++j) {
       if (o[j].is_none()) continue;
       Tensor x = dev_input(o[j].cast<Tensor>(), j < 3 ? at::kFloat : at::kInt, PLANES[j], NO_CPU_P, &dev);
-      if (x.dim() != 2 || x.size(0) != H || x.size(1) != W) throw py::value_error(std::string("blend_pixel_maps: ") + PLANES[j] + " is [H, W]");
+      if (x.dim() != 2 || x.size(0) != s.H || x.size(1) != s.W) throw py::value_error(std::string("blend_pixel_maps: ") + PLANES[j] + " is [H, W]");
       if (!x.is_contiguous()) throw py::value_error("blend_pixel_maps: the planes are written in place and must be contiguous");
       keep.push_back(x);
       ptr[j] = x.data_ptr();

@@ -1,9 +1,7 @@
 // Segmentation from 2D label planes (binocular3dgs_amd/segment.py): launch assembly of b3gs_label_votes_batch and
 // b3gs_label_render_batch over the state buffers a FusedRasterizer forward left in its slots.  No autograd: votes and label
 // maps are not differentiable.
-#include "common.h"
-
-#include <vector>
+#include "walk_state.h"
 
 namespace py = pybind11;
 using at::Tensor;
@@ -11,27 +9,6 @@ using at::Tensor;
 namespace b3 {
 
 static const char* NO_CPU_S = "the label votes and label renders run on the HIP device only (there is no host statement of the tile walk)";
-
-// The three uint8 state buffers of one view's forward and its size out of the head of a view tuple -> the tensors are
-// pushed to `keep`, the scene is filled.
-struct ViewState {
-  const char *geometry, *binning, *image;
-  int64_t W, H;
-};
-static ViewState view_state(const py::tuple& t, int64_t P, const at::Device& dev, std::vector<Tensor>& keep, B3gsScene& sc,
-                            const char* fn) {
-  Tensor geom = dev_input(t[0].cast<Tensor>(), at::kByte, "geometry", NO_CPU_S, &dev);
-  Tensor binning = dev_input(t[1].cast<Tensor>(), at::kByte, "binning", NO_CPU_S, &dev);
-  Tensor img = dev_input(t[2].cast<Tensor>(), at::kByte, "image", NO_CPU_S, &dev);
-  const int64_t W = t[3].cast<int64_t>(), H = t[4].cast<int64_t>();
-  if (W <= 0 || H <= 0 || W > INT32_MAX || H > INT32_MAX) throw py::value_error(std::string(fn) + ": W and H must be positive");
-  if (geom.numel() < (int64_t)b3gs_geometry_bytes((int32_t)P) || img.numel() < (int64_t)b3gs_image_bytes((int32_t)W, (int32_t)H))
-    throw py::value_error(std::string(fn) + ": a state buffer is smaller than its P / W x H ask for");
-  for (const Tensor& x : {geom, binning, img}) keep.push_back(x);
-  sc = B3gsScene{};
-  sc.P = (int32_t)P, sc.W = (int32_t)W, sc.H = (int32_t)H;
-  return ViewState{(const char*)geom.data_ptr(), (const char*)binning.data_ptr(), (const char*)img.data_ptr(), W, H};
-}
 
 // views: 1..8 tuples (geometry, binning, image, W, H, labels) -- labels a uint8 [H,W] tensor; votes_q32: int64 [P, nlabels],
 // contiguous, accumulated into (its bits are the library's uint64 words).
@@ -53,7 +30,7 @@ static void label_votes(const py::list& views, int64_t nlabels, Tensor votes_q32
   for (size_t k = 0; k < n; ++k) {
     py::tuple t = views[k].cast<py::tuple>();
     if (t.size() != 6) throw py::value_error("label_votes: a view is (geometry, binning, image, W, H, labels)");
-    const ViewState s = view_state(t, P, dev, keep, sc[k], "label_votes");
+    const ViewState s = view_state(t, 3, P, &dev, keep, sc[k], "label_votes", NO_CPU_S);
     Tensor lab = dev_input(t[5].cast<Tensor>(), at::kByte, "labels", NO_CPU_S, &dev);
     if (lab.numel() != s.W * s.H) throw py::value_error("label_votes: a label plane holds H * W bytes");
     lab = lab.contiguous();
@@ -85,7 +62,7 @@ static void label_render(const py::list& views, int64_t nlabels, Tensor gaussian
   for (size_t k = 0; k < n; ++k) {
     py::tuple t = views[k].cast<py::tuple>();
     if (t.size() != 7) throw py::value_error("label_render: a view is (geometry, binning, image, W, H, label, weight)");
-    const ViewState s = view_state(t, P, dev, keep, sc[k], "label_render");
+    const ViewState s = view_state(t, 3, P, &dev, keep, sc[k], "label_render", NO_CPU_S);
     Tensor label = dev_input(t[5].cast<Tensor>(), at::kByte, "label", NO_CPU_S, &dev);
     Tensor weight = dev_input(t[6].cast<Tensor>(), at::kFloat, "weight", NO_CPU_S, &dev);
     for (const Tensor* x : {&label, &weight}) {

@@ -96,6 +96,16 @@ def _batches(model, cameras: Sequence, bg: torch.Tensor, batch: int, capacity: O
                 yield idx[c0:c0 + batch], (outs if full else [o["render"] for o in outs])
 
 
+def _walk_batches(model, cameras: Sequence, bg: torch.Tensor, batch: int, capacity: Optional[int] = None):
+    """_batches(full=True) for the calls that walk the forward's tile lists a second time (importance, pixel_maps, segment):
+    yields (indices into `cameras`, per-view output dicts, W, H, slots) per launch -- slots[k] holds the state buffers
+    (geom, binning, img) the forward of camera idx[k] left (_render_checked renders camera k of a launch into slot k)."""
+    for idx, outs in _batches(model, cameras, bg, batch, capacity, full=True):
+        cam0 = cameras[idx[0]]
+        W, H = int(cam0.image_width), int(cam0.image_height)
+        yield idx, outs, W, H, model.__dict__["_b3gs_eval_renderers"][(W, H)].slots[:len(idx)]
+
+
 def render_views(model, cameras: Sequence, bg: torch.Tensor, *, batch: int = MAX_BATCH,
                  capacity: Optional[int] = None) -> List[torch.Tensor]:
     """render(cam, model, pipe, bg)["render"] under no_grad for every camera, up to `batch` (<= 8) views of the same

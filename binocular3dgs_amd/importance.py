@@ -43,7 +43,7 @@ def contributions(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, bat
     """The four statistics of every Gaussian of `model` over `cameras`, device tensors [P].
     masks: None, or per camera None or an [H,W] tensor (nonzero / True = count the pixel; a DTU camera's object mask, say)."""
     from . import _C
-    from .evaluate import _batches
+    from .evaluate import _walk_batches
     if masks is not None and len(masks) != len(cameras):
         raise ValueError("one mask (or None) per camera")
     dev = model.get_xyz.device
@@ -54,13 +54,9 @@ def contributions(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, bat
     # The device counters are 32-bit words: folded into 64-bit sums and zeroed after every launch, so that no camera set can
     # wrap them (one launch counts at most 8 W H pixels).  The weight words are 64-bit already.
     hits, dominant = torch.zeros(P, dtype=torch.int64, device=dev), torch.zeros(P, dtype=torch.int64, device=dev)
-    for idx, _outs in _batches(model, cameras, bg, batch, capacity, full=True):
-        cam0 = cameras[idx[0]]
-        W, H = int(cam0.image_width), int(cam0.image_height)
-        fr = model.__dict__["_b3gs_eval_renderers"][(W, H)]
+    for idx, _outs, W, H, slots in _walk_batches(model, cameras, bg, batch, capacity):
         views = []
-        for k, i in enumerate(idx):      # (evaluate._render_checked renders camera k of a launch into slot k)
-            s = fr.slots[k]
+        for i, s in zip(idx, slots):
             m = None if masks is None or masks[i] is None else (masks[i].reshape(H, W) != 0).to(device=dev, dtype=torch.uint8)
             views.append((s.geom, s.binning, s.img, W, H, m))
         _C.blend_contribution(views, wq, hits32, wmax_bits, dom32)

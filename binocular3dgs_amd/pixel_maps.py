@@ -39,19 +39,15 @@ def plane_batches(model, cameras: Sequence, bg: torch.Tensor, planes: Sequence[s
     launch.  planes: names out of median_depth, depth_m1, depth_m2 (float32 [H,W]), dominant, count (int32 [H,W]): fresh
     tensors, the caller's to keep.  The output dicts are the renderer's slot buffers: valid until the next item is drawn."""
     from . import _C
-    from .evaluate import _batches
+    from .evaluate import _walk_batches
     unknown = [p for p in planes if p not in _PLANES]
     if unknown:
         raise ValueError(f"planes are out of {_PLANES}, not {unknown}")
     dev = model.get_xyz.device
     P = model.get_xyz.shape[0]
-    for idx, outs in _batches(model, cameras, bg, batch, capacity, full=True):
-        cam0 = cameras[idx[0]]
-        W, H = int(cam0.image_width), int(cam0.image_height)
-        fr = model.__dict__["_b3gs_eval_renderers"][(W, H)]
+    for idx, outs, W, H, slots in _walk_batches(model, cameras, bg, batch, capacity):
         views, tables, raws = [], [], []
-        for k in range(len(idx)):        # (evaluate._render_checked renders camera k of a launch into slot k)
-            s = fr.slots[k]
+        for s in slots:
             views.append((s.geom, s.binning, s.img, P, W, H))
             raw = {}
             for name in _PLANES:

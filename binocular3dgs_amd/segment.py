@@ -58,7 +58,7 @@ def label_votes(model, cameras: Sequence, bg: torch.Tensor, labels: Sequence, n_
     """int64 [P, n_labels] on the device: votes[g, l] = sum of rint(w 2^32) over the pixels labelled l of all cameras;
     votes.double() / 2**32 is the weight.  labels: per camera None (the camera is skipped) or a uint8 [H,W] tensor."""
     from . import _C
-    from .evaluate import _batches
+    from .evaluate import _walk_batches
     L = _check_n(n_labels)
     if len(labels) != len(cameras):
         raise ValueError("one label plane (or None) per camera")
@@ -69,13 +69,9 @@ def label_votes(model, cameras: Sequence, bg: torch.Tensor, labels: Sequence, n_
     if not used or P == 0:
         return votes
     cams = [cameras[i] for i in used]
-    for idx, _outs in _batches(model, cams, bg, batch, capacity, full=True):
-        cam0 = cams[idx[0]]
-        W, H = int(cam0.image_width), int(cam0.image_height)
-        fr = model.__dict__["_b3gs_eval_renderers"][(W, H)]
+    for idx, _outs, W, H, slots in _walk_batches(model, cams, bg, batch, capacity):
         views = []
-        for k, i in enumerate(idx):      # (evaluate._render_checked renders camera k of a launch into slot k)
-            s = fr.slots[k]
+        for i, s in zip(idx, slots):
             plane = labels[used[i]]
             if plane.dtype != torch.uint8 or plane.numel() != H * W:
                 raise ValueError(f"camera {used[i]}: a label plane is uint8 [H,W] = [{H},{W}]")
@@ -115,7 +111,7 @@ def render_labels(model, cameras: Sequence, bg: torch.Tensor, gaussian_labels: t
     launch by launch (cameras of one size together, otherwise in order): per pixel the label whose Gaussians hold the largest
     sum of blend weights (255: none) and that sum.  All tensors are the caller's to keep."""
     from . import _C
-    from .evaluate import _batches
+    from .evaluate import _walk_batches
     L = _check_n(n_labels)
     dev = model.get_xyz.device
     P = model.get_xyz.shape[0]
@@ -123,13 +119,9 @@ def render_labels(model, cameras: Sequence, bg: torch.Tensor, gaussian_labels: t
     if gl.dtype != torch.uint8 or gl.shape != (P,):
         raise ValueError("gaussian_labels is uint8 [P]")
     gl = gl.to(dev).contiguous()
-    for idx, outs in _batches(model, cameras, bg, batch, capacity, full=True):
-        cam0 = cameras[idx[0]]
-        W, H = int(cam0.image_width), int(cam0.image_height)
-        fr = model.__dict__["_b3gs_eval_renderers"][(W, H)]
+    for idx, outs, W, H, slots in _walk_batches(model, cameras, bg, batch, capacity):
         views, res = [], []
-        for k in range(len(idx)):        # (evaluate._render_checked renders camera k of a launch into slot k)
-            s = fr.slots[k]
+        for s in slots:
             # (the launch writes every pixel; without Gaussians there is no launch)
             label = torch.empty((H, W), dtype=torch.uint8, device=dev) if P else torch.full((H, W), NO_LABEL, dtype=torch.uint8, device=dev)
             weight = torch.empty((H, W), dtype=torch.float32, device=dev) if P else torch.zeros((H, W), device=dev)
