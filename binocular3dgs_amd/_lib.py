@@ -244,7 +244,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_transform_points", "b3gs_transform_gaussians", "b3gs_select_gaussians", "b3gs_nearest_query_index",
            "b3gs_similarity_sums_workspace_bytes", "b3gs_similarity_sums",
            # added to ABI 18: the camera pose gradient
-           "b3gs_pose_gradient_workspace_bytes", "b3gs_pose_gradient")
+           "b3gs_pose_gradient_workspace_bytes", "b3gs_pose_gradient",
+           # added to ABI 18: merging Gaussians into levels of detail
+           "b3gs_gaussian_merge_workspace_bytes", "b3gs_gaussian_merge_count", "b3gs_gaussian_merge_emit")
 
 _lib = None
 
@@ -478,6 +480,12 @@ def lib():
     L.b3gs_similarity_sums_workspace_bytes.restype = C.c_size_t
     L.b3gs_similarity_sums.argtypes = [I64, V, I64, V, V, V, F, V, C.POINTER(C.c_double), C.POINTER(C.c_double), V, V, V]
     L.b3gs_similarity_sums.restype = C.c_int
+    L.b3gs_gaussian_merge_workspace_bytes.argtypes = [I64, I32]
+    L.b3gs_gaussian_merge_workspace_bytes.restype = C.c_size_t
+    L.b3gs_gaussian_merge_count.argtypes = [I32, I32, V, V, V, V, V, V, V, F, V, V]
+    L.b3gs_gaussian_merge_count.restype = C.c_int
+    L.b3gs_gaussian_merge_emit.argtypes = [I32, I32, V, V, V, V, V, V, V, F, V, C.POINTER(C.c_int64), V, V, V, V, V, V, V, V, V]
+    L.b3gs_gaussian_merge_emit.restype = C.c_int
     L.b3gs_pose_gradient_workspace_bytes.argtypes = [I32, I32]
     L.b3gs_pose_gradient_workspace_bytes.restype = C.c_size_t
     L.b3gs_pose_gradient.argtypes = [I32, I32, I32, V, V, V, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

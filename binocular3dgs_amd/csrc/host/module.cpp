@@ -67,4 +67,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_undistort(m);
   b3::bind_edit(m);
   b3::bind_pose(m);
+  b3::bind_lod(m);
 }

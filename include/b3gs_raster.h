@@ -1385,6 +1385,74 @@ int b3gs_pose_gradient(int32_t P, int32_t sh_degree, int32_t nviews, const float
                        const float* const* grad_features_rest, const uint8_t* const* skip, const double* pivot, double* out,
                        void* workspace, b3gs_stream_t stream);
 
+/* ---- merging Gaussians: moment-matched levels of detail (added to ABI 18; csrc/lod.hip, binocular3dgs_amd/lod.py, INTEGRATION.md
+ * section 26) ------------------------------------------------------------------------------------------------------------------
+ * Three entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * The mergeable Gaussians of one grid cell are replaced by the ONE Gaussian with the mass-weighted mean and covariance of their
+ * mixture.  The inputs are ACTIVATED float32 values: positions [P,3], scales [P,3] > 0, quaternions [P,4] (w, x, y, z; any
+ * non-zero norm), opacities [P] in (0, 1), features_dc [P,3], features_rest [P, K, 3] with K in {0, 3, 8, 15} coefficients
+ * per channel, an optional float64 weights [P] >= 0 (NULL: none), a float32 cell > 0.  P < 2^24.  No exp, log or sigmoid runs
+ * here: only + - * / sqrt and comparisons, in fp64 unless stated, every statement ONE operation (the translation unit is
+ * compiled with -ffp-contract=off), one thread per output in one fixed order: tests/lod_ref.py restates every statement and
+ * every output agrees bit for bit.  No floating-point atomic, no vendor library, no host read.
+ *
+ * 1. box        o = the per-axis float32 minimum of the positions.  A row (Gaussian) with a value that is not finite in ANY
+ *               input is counted, once.  c_a = floor((x_a - o_a) / cell): two rounded float32 operations, then the floor.  A
+ *               c_a outside 0 .. 1023 (or NaN) is counted, not clamped.  key = (c_z << 20) | (c_y << 10) | c_x.
+ * 2. mergeable  max(s_0, s_1, s_2) <= cell, compared in float32.  A Gaussian that is not mergeable passes through untouched.
+ * 3. clusters   the mergeable Gaussians of one key, in index order (a stable sort by key).
+ * 4. order      output rows: the clusters in ascending key order, then the pass-throughs in index order.  A cluster of one
+ *               member and every pass-through is a copy of its input words, bit for bit (the quaternion as given).
+ * 5. a cluster of n >= 2 members i (in order) makes one Gaussian:
+ *      v_i = (s_0 s_1) s_2,  a_i = alpha_i v_i,  A = sum a_i,  W = sum w_i a_i        (each sum from +0, one addition per member)
+ *      m_i = w_i a_i and M = W when weights are given and W != 0; otherwise m_i = a_i and M = A
+ *      S_a = sum m_i x_ia;  mu_a = S_a / M
+ *      per member: n = sqrt(((w w + x x) + y y) + z z) of its quaternion, (w, x, y, z) each / n,
+ *        R = [1 - 2 (y y + z z), 2 (x y - w z), 2 (x z + w y);  2 (x y + w z), 1 - 2 (x x + z z), 2 (y z - w x);
+ *             2 (x z - w y), 2 (y z + w x), 1 - 2 (x x + y y)],   u_k = s_k s_k,   d_a = x_ia - mu_a,
+ *        cov_ab = ((R_a0 u_0) R_b0 + (R_a1 u_1) R_b1) + (R_a2 u_2) R_b2
+ *        C_ab = C_ab + m_i (cov_ab + d_a d_b)          for the six entries 00, 01, 02, 11, 12, 22
+ *      Sigma_ab = C_ab / M
+ *      eigen-decomposition: cyclic Jacobi, V = I, B3GS_MERGE_JACOBI_SWEEPS sweeps over (p, q) = (0,1), (0,2), (1,2); a
+ *        rotation is skipped when a_pq == 0, else with r the third index
+ *          theta = (a_qq - a_pp) / (2 a_pq);  t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta theta + 1))
+ *          c = 1 / sqrt(t t + 1);  s = t c;  tau = t a_pq;  a_pp = a_pp - tau;  a_qq = a_qq + tau;  a_pq = 0
+ *          (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq);  per row k of V: (v_kp, v_kq) = (c v_kp - s v_kq, s v_kp + c v_kq)
+ *        lambda = the diagonal, sorted descending with its columns of V by insertion (strict >: ties keep column order);
+ *        det V = (v00 (v11 v22 - v12 v21) - v01 (v10 v22 - v12 v20)) + v02 (v10 v21 - v11 v20) < 0: the third column is negated
+ *      floor: f = z z with z the smallest float32 scale of any member; lambda_k < f: lambda_k = f.  s'_k = sqrt(lambda_k)
+ *      quaternion of V by Shepperd's branches, T = (v00 + v11) + v22:
+ *        T > 0:                     g = 2 sqrt(T + 1):                  (g / 4, (v21 - v12) / g, (v02 - v20) / g, (v10 - v01) / g)
+ *        else v00 > v11, v00 > v22: g = 2 sqrt(((1 + v00) - v11) - v22): ((v21 - v12) / g, g / 4, (v01 + v10) / g, (v02 + v20) / g)
+ *        else v11 > v22:            g = 2 sqrt(((1 + v11) - v00) - v22): ((v02 - v20) / g, (v01 + v10) / g, g / 4, (v12 + v21) / g)
+ *        else:                      g = 2 sqrt(((1 + v22) - v00) - v11): ((v10 - v01) / g, (v02 + v20) / g, (v12 + v21) / g, g / 4)
+ *        (g / 4 is 0.25 g), divided by its norm as above, all four negated when w < 0
+ *      opacity: alpha' = A / ((s'_0 s'_1) s'_2), clamped to [1 / 255, 0.99]: the mass sum a_i is preserved where the clamp
+ *        does not bite; unlike m_i it does not use the weights
+ *      colour: every channel f of features_dc and features_rest: (sum m_i f_i) / M, from +0, members in order
+ *      every output is rounded once to float32.
+ *    The sweep count is the smallest at which tests/lod_ref.py agrees with numpy.linalg.eigh to 1e-13 (relative to the largest
+ *    eigenvalue, eigenvalues and V diag(lambda) V^T) on 10^5 random and degenerate symmetric 3 x 3 matrices.
+ *
+ * count leaves int64 words at the START of the workspace: {clusters, pass-throughs, merged members (members of clusters with
+ * n >= 2), rows that are not finite, rows beyond the 1024 cells of an axis}, then two more {output rows = clusters +
+ * pass-throughs, the float32 bits of the largest box edge}.  The caller reads them ONCE and hands the first five to emit as a
+ * HOST array; emit fails with B3GS_ERR_ARG and the count in b3gs_last_error() when either error word is not zero, otherwise
+ * fills the outputs ([rows, ..]), cluster_of [P] (the output row of every input) and members [rows] (the member count of
+ * every output row), and writes nothing past `rows` rows.  emit takes the arguments of count and the same workspace
+ * (256-byte aligned, b3gs_gaussian_merge_workspace_bytes(P, K) bytes, about 70 bytes per Gaussian; 0 for bad sizes).
+ * A cluster may have any number of members (one thread walks them). */
+#define B3GS_MERGE_JACOBI_SWEEPS 4
+size_t b3gs_gaussian_merge_workspace_bytes(int64_t P, int32_t K);
+int b3gs_gaussian_merge_count(int32_t P, int32_t K, const float* positions, const float* scales, const float* quaternions,
+                              const float* opacities, const float* features_dc, const float* features_rest, const double* weights,
+                              float cell, void* workspace, b3gs_stream_t stream);
+int b3gs_gaussian_merge_emit(int32_t P, int32_t K, const float* positions, const float* scales, const float* quaternions,
+                             const float* opacities, const float* features_dc, const float* features_rest, const double* weights,
+                             float cell, void* workspace, const int64_t* totals, float* out_positions, float* out_scales,
+                             float* out_quaternions, float* out_opacities, float* out_features_dc, float* out_features_rest,
+                             int32_t* cluster_of, int32_t* members, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
