@@ -246,7 +246,10 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: the camera pose gradient
            "b3gs_pose_gradient_workspace_bytes", "b3gs_pose_gradient",
            # added to ABI 18: merging Gaussians into levels of detail
-           "b3gs_gaussian_merge_workspace_bytes", "b3gs_gaussian_merge_count", "b3gs_gaussian_merge_emit")
+           "b3gs_gaussian_merge_workspace_bytes", "b3gs_gaussian_merge_count", "b3gs_gaussian_merge_emit",
+           # added to ABI 18: screened Poisson surface reconstruction
+           "b3gs_oriented_points_workspace_bytes", "b3gs_oriented_points_batch", "b3gs_oriented_points_emit",
+           "b3gs_poisson_workspace_bytes", "b3gs_poisson_splat", "b3gs_poisson_apply", "b3gs_poisson_solve", "b3gs_poisson_volume")
 
 _lib = None
 
@@ -486,6 +489,22 @@ def lib():
     L.b3gs_gaussian_merge_count.restype = C.c_int
     L.b3gs_gaussian_merge_emit.argtypes = [I32, I32, V, V, V, V, V, V, V, F, V, C.POINTER(C.c_int64), V, V, V, V, V, V, V, V, V]
     L.b3gs_gaussian_merge_emit.restype = C.c_int
+    L.b3gs_oriented_points_workspace_bytes.argtypes = [I32, I32, I32]
+    L.b3gs_oriented_points_workspace_bytes.restype = C.c_size_t
+    L.b3gs_oriented_points_batch.argtypes = [I32, C.POINTER(B3gsTsdfView), I32, I32, I32, F, F, F, I32, V, V]
+    L.b3gs_oriented_points_batch.restype = C.c_int
+    L.b3gs_oriented_points_emit.argtypes = [I32, C.POINTER(B3gsTsdfView), I32, I32, I32, F, F, F, I32, V, I64, V, V, V, V, V]
+    L.b3gs_oriented_points_emit.restype = C.c_int
+    L.b3gs_poisson_workspace_bytes.argtypes = [I32, I32, I32, I64]
+    L.b3gs_poisson_workspace_bytes.restype = C.c_size_t
+    L.b3gs_poisson_splat.argtypes = [C.POINTER(B3gsTsdfVolume), I64, V, V, V, V, V, V, V]
+    L.b3gs_poisson_splat.restype = C.c_int
+    L.b3gs_poisson_apply.argtypes = [C.POINTER(B3gsTsdfVolume), V, F, V, V, V]
+    L.b3gs_poisson_apply.restype = C.c_int
+    L.b3gs_poisson_solve.argtypes = [C.POINTER(B3gsTsdfVolume), V, V, F, I32, F, I32, V, V, V, V]
+    L.b3gs_poisson_solve.restype = C.c_int
+    L.b3gs_poisson_volume.argtypes = [C.POINTER(B3gsTsdfVolume), V, V, I32, V, V]
+    L.b3gs_poisson_volume.restype = C.c_int
     L.b3gs_pose_gradient_workspace_bytes.argtypes = [I32, I32]
     L.b3gs_pose_gradient_workspace_bytes.restype = C.c_size_t
     L.b3gs_pose_gradient.argtypes = [I32, I32, I32, V, V, V, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

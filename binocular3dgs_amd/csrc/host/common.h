@@ -90,5 +90,6 @@ void bind_undistort(pybind11::module_& m);
 void bind_edit(pybind11::module_& m);
 void bind_pose(pybind11::module_& m);
 void bind_lod(pybind11::module_& m);
+void bind_poisson(pybind11::module_& m);
 
 }  // namespace b3

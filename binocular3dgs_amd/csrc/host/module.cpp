@@ -68,4 +68,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_edit(m);
   b3::bind_pose(m);
   b3::bind_lod(m);
+  b3::bind_poisson(m);
 }

@@ -1,6 +1,8 @@
 """python -m binocular3dgs_amd.extract_mesh -m MODEL_PATH [-s SOURCE_PATH] [--iteration -1] [--views train|test|all]
                                             [--resolution 256 | --voxel_size S] [--truncation_voxels 4] [--alpha_min 0.5]
                                             [--min_weight 1] [--depth mean|median] [--bounds x0 y0 z0 x1 y1 z1]
+                                            [--method tsdf|poisson [--screen 4] [--poisson_iters K] [--poisson_tol 1e-4]
+                                             [--sample_stride 1] [--spread 1] [--trim 0]]
                                             [--keep_largest 0] [--min_triangles 0] [--cull_unseen [--min_pixels 1]]
                                             [--smooth N [--smooth_lambda 0.5] [--smooth_mu -0.53] [--free_boundary]] [--normals]
                                             [--simplify K | --target_triangles N] [--placement quadric|mean]
@@ -12,7 +14,13 @@ the chosen cameras, depth, alpha and colour are fused into a TSDF volume and the
 device (mesh.fuse_model).  Writes <model_path>/mesh/iteration_<it>/mesh.ply (binary PLY, coloured vertices) and prints the
 voxel, vertex and triangle counts.  --depth median fuses the depth at which a pixel's transmittance crosses one half
 (pixel_maps.py) in place of the alpha-weighted mean, which lies between the surfaces where a semi-transparent Gaussian hangs in
-front of one.  --keep_largest K keeps the K components with the most triangles (ties at the K-th
+front of one.  --method poisson fits one smooth function to oriented samples of the same renders (poisson.py: screened Poisson
+reconstruction, conjugate gradients on the device) in place of the TSDF, whose surface only exists where a view looked: the mesh
+is closed also behind what the views saw.  --screen weighs the samples against smoothness, --poisson_iters and --poisson_tol
+bound the solver (default: four times the longest axis, relative residual 1e-4), --sample_stride takes every S-th pixel, --trim W > 0
+keeps only the cells whose corners have W of sample weight within --spread nodes (0: every cell, the watertight mesh).  It
+composes with --depth median and every step below, and prints the iterations done, the final relative residual and the
+topology line of the extracted mesh.  --keep_largest K keeps the K components with the most triangles (ties at the K-th
 all survive), --min_triangles M the components with at least M (mesh_tools.clean); with both at 0 the step is not run.
 --cull_unseen renders the mesh into the cameras of --views (mesh_render.cull_unseen) and drops the triangles that win fewer
 than --min_pixels pixels over all of them, e.g. blobs inside or behind the observed surface; it runs after the cleaning step
@@ -65,6 +73,13 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--min_weight", type=float, default=1.0)
     p.add_argument("--depth", choices=("mean", "median"), default="mean",
                    help="the depth of a pixel that is fused: the alpha-weighted mean, or the depth at which the transmittance crosses 1/2")
+    p.add_argument("--method", choices=("tsdf", "poisson"), default="tsdf", help="TSDF fusion, or a screened Poisson fit of oriented samples (watertight)")
+    p.add_argument("--screen", type=_positive_float, default=None, metavar="A", help="with --method poisson: weight of the samples (default 4)")
+    p.add_argument("--poisson_iters", type=_positive_int, default=None, metavar="K", help="with --method poisson: CG iterations (default 4 x longest axis)")
+    p.add_argument("--poisson_tol", type=float, default=None, metavar="T", help="with --method poisson: relative residual that stops the solver (default 1e-4)")
+    p.add_argument("--sample_stride", type=_positive_int, default=None, metavar="S", help="with --method poisson: every S-th pixel is a sample (default 1)")
+    p.add_argument("--spread", type=int, default=None, metavar="R", help="with --method poisson: nodes around a node whose sample weight supports it (default 1)")
+    p.add_argument("--trim", type=float, default=None, metavar="W", help="with --method poisson: drop cells with less support than W (default 0: watertight)")
     p.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
     p.add_argument("--keep_largest", type=int, default=0, help="keep the K largest connected components (0: all)")
     p.add_argument("--min_triangles", type=int, default=0, help="drop the components with fewer triangles (0: none)")
@@ -145,7 +160,8 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
         keep_largest: int = 0, min_triangles: int = 0, simplify=None, target_triangles=None, placement: str = "quadric",
         cull_unseen: bool = False, min_pixels: int = 1, texture: bool = False, texel_cell=None, atlas_side=None,
         texture_from: str = "render", texture_slack=None, two_sided: bool = False, smooth=None, smooth_lambda: float = 0.5,
-        smooth_mu: float = -0.53, free_boundary: bool = False, normals: bool = False, depth: str = "mean") -> str:
+        smooth_mu: float = -0.53, free_boundary: bool = False, normals: bool = False, depth: str = "mean", method: str = "tsdf",
+        screen=None, poisson_iters=None, poisson_tol=None, sample_stride: int = 1, spread: int = 1, trim: float = 0.0) -> str:
     from . import mesh
     from .gaussian_model import GaussianModel
     from .spiral import max_iteration, read_cfg_args
@@ -159,9 +175,17 @@ def run(model_path: str, source_path=None, iteration: int = -1, views: str = "tr
     white = bool(cfg.get("white_background", False))
     bg = torch.tensor([1.0, 1.0, 1.0] if white else [0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
     t0 = time.perf_counter()
+    solver = {}
     vertices, colours, faces, vol = mesh.fuse_model(
         model, cams, bg, resolution=resolution, voxel_size=voxel_size, bounds=None if bounds is None else (bounds[:3], bounds[3:]),
-        truncation_voxels=truncation_voxels, alpha_min=alpha_min, min_weight=min_weight, return_volume=True, depth=depth)
+        truncation_voxels=truncation_voxels, alpha_min=alpha_min, min_weight=min_weight, return_volume=True, depth=depth, method=method,
+        screen=screen, poisson_iters=poisson_iters, poisson_tol=poisson_tol, sample_stride=sample_stride, spread=spread, trim=trim, info=solver)
+    if method == "poisson":
+        from . import mesh_tools
+        print(f"poisson: {solver['samples']} samples ({solver['dropped']} outside the grid), {solver['iterations']} iterations, "
+              f"relative residual {solver['residual']:.3e}")
+        if faces.shape[0]:
+            print(mesh_tools.topology_line(mesh_tools.topology(vertices, faces)))
     if keep_largest or min_triangles:
         from . import mesh_tools
         vertices, colours, faces, st = mesh_tools.clean(vertices, colours, faces, keep_largest, min_triangles, return_stats=True)
@@ -249,11 +273,21 @@ def main(argv=None) -> int:
         p.error("--smooth_lambda is in (0, 1]")
     if not (mu == 0.0 or mu < -lam):
         p.error("--smooth_mu is below -lambda, or 0")
+    if a.method != "poisson" and any(v is not None for v in (a.screen, a.poisson_iters, a.poisson_tol, a.sample_stride, a.spread, a.trim)):
+        p.error("--screen, --poisson_iters, --poisson_tol, --sample_stride, --spread and --trim need --method poisson")
+    if a.poisson_tol is not None and not (a.poisson_tol >= 0.0 and a.poisson_tol < float("inf")):
+        p.error("--poisson_tol is at least 0 and finite")
+    if a.spread is not None and not 0 <= a.spread <= 1024:
+        p.error("--spread is 0 .. 1024")
+    if a.trim is not None and not (a.trim >= 0.0 and a.trim < float("inf")):
+        p.error("--trim is at least 0 and finite")
     if a.texture_slack is not None and not (a.texture_slack >= 0.0 and a.texture_slack < float("inf")):
         p.error("--texture_slack is at least 0 and finite")
     run(a.model_path, a.source_path, a.iteration, a.views, a.resolution, a.voxel_size, a.truncation_voxels, a.alpha_min,
         a.min_weight, a.bounds, a.keep_largest, a.min_triangles, a.simplify, a.target_triangles, a.placement, a.cull_unseen, a.min_pixels,
-        a.texture, a.texel_cell, a.atlas_side, a.texture_from, a.texture_slack, a.two_sided, a.smooth, lam, mu, a.free_boundary, a.normals, a.depth)
+        a.texture, a.texel_cell, a.atlas_side, a.texture_from, a.texture_slack, a.two_sided, a.smooth, lam, mu, a.free_boundary, a.normals, a.depth,
+        a.method, a.screen, a.poisson_iters, a.poisson_tol, 1 if a.sample_stride is None else a.sample_stride, 1 if a.spread is None else a.spread,
+        0.0 if a.trim is None else a.trim)
     return 0
 
 

@@ -26,6 +26,7 @@ import torch
 MAX_VIEWS = 8          # views per integrate launch (B3GS_MAX_TSDF_VIEWS)
 MAX_DIM = 1024         # voxels per axis (B3GS_MAX_TSDF_DIM)
 DEPTHS = ("mean", "median")   # the depth of a pixel that fuse_model fuses
+METHODS = ("tsdf", "poisson")  # how fuse_model turns the views into a surface
 NEAR = 0.2             # the renderer's near plane (B3GS_NEAR): a voxel nearer to a camera than this is not seen by it
 
 
@@ -55,7 +56,21 @@ class TsdfVolume:
         dims = [max(2, int(math.ceil((h - l) / voxel_size - 1e-4))) for l, h in zip(lo, hi)]
         if max(dims) > MAX_DIM:
             raise ValueError(f"TsdfVolume: {dims[0]} x {dims[1]} x {dims[2]} voxels; at most {MAX_DIM} per axis (use a larger voxel)")
-        self.origin, self.voxel_size, self.dims = lo, voxel_size, tuple(dims)
+        self._allocate(lo, voxel_size, dims, truncation, device)
+
+    @classmethod
+    def from_dims(cls, origin, dims, voxel_size: float, truncation: Optional[float] = None, device="cuda") -> "TsdfVolume":
+        """A volume of exactly nx x ny x nz voxels (any size from 1; the bounds constructor rounds up to at least 2 per axis)."""
+        dims = [int(d) for d in dims]
+        voxel_size = float(voxel_size)
+        if len(dims) != 3 or len(origin) != 3 or min(dims) < 1 or max(dims) > MAX_DIM or not voxel_size > 0.0:
+            raise ValueError(f"TsdfVolume.from_dims: three sizes of 1 .. {MAX_DIM}, an origin and a positive voxel size are needed")
+        self = cls.__new__(cls)
+        self._allocate([float(v) for v in origin], voxel_size, dims, truncation, device)
+        return self
+
+    def _allocate(self, origin, voxel_size, dims, truncation, device):
+        self.origin, self.voxel_size, self.dims = origin, voxel_size, tuple(dims)
         self.truncation = 4.0 * voxel_size if truncation is None else float(truncation)
         if not self.truncation > 0.0:
             raise ValueError("TsdfVolume: the truncation is positive")
@@ -118,7 +133,9 @@ def scene_bounds(model, quantile: float = 0.01, pad: float = 0.0):
 
 def fuse_model(model, cameras: Sequence, bg: torch.Tensor, *, resolution: Optional[int] = None, voxel_size: Optional[float] = None,
                bounds=None, truncation_voxels: float = 4.0, alpha_min: float = 0.5, min_weight: float = 1.0, quantile: float = 0.01,
-               batch: int = MAX_VIEWS, return_volume: bool = False, depth: str = "mean"):
+               batch: int = MAX_VIEWS, return_volume: bool = False, depth: str = "mean", method: str = "tsdf", screen: Optional[float] = None,
+               poisson_iters: Optional[int] = None, poisson_tol: Optional[float] = None, sample_stride: int = 1, spread: int = 1,
+               trim: float = 0.0, info: Optional[dict] = None):
     """Renders `cameras` and fuses depth, alpha and colour into a volume, batch by batch out of the renderer's slot buffers
     (no clones, no host copies), then extracts the mesh.  At most one of resolution (voxels along the longest axis of the
     bounds; default 256) and voxel_size; bounds = (min [3], max [3]), default scene_bounds(), which is then widened by the
@@ -127,10 +144,19 @@ def fuse_model(model, cameras: Sequence, bg: torch.Tensor, *, resolution: Option
     rendered_alpha -- between the surfaces where a semi-transparent Gaussian hangs in front of one.  "median": the depth at
     which the transmittance crosses one half (pixel_maps.py), always a depth at which a Gaussian sits.  The integration
     kernel divides its depth input by alpha, so it is handed median_depth * alpha: what it fuses is the median to one float32
-    rounding (x * a / a is within one unit in the last place of x)."""
+    rounding (x * a / a is within one unit in the last place of x).
+    method: "tsdf" (the default, described above) or "poisson": every sample_stride-th pixel of the same renders becomes an
+    oriented sample (poisson.oriented_points; the median depth is handed over as it is), a screened Poisson fit over the same
+    grid gives one smooth function (screen, poisson_iters, poisson_tol: poisson.PoissonVolume.solve's defaults when None) and
+    its level set is extracted: closed wherever it stays inside the grid, also behind what the views saw.  `trim` then plays
+    min_weight's part (0: every cell; W > 0: only cells whose corners have that much sample weight within `spread` nodes), the
+    vertex colours are those of the nearest sample, the volume returned is the one the extractor read, and `info` (a dict)
+    receives the solver's iteration count and residual."""
     from .evaluate import _batches
     if depth not in DEPTHS:
         raise ValueError(f"fuse_model: depth is one of {DEPTHS}")
+    if method not in METHODS:
+        raise ValueError(f"fuse_model: method is one of {METHODS}")
     if resolution is not None and voxel_size is not None:
         raise ValueError("fuse_model: resolution or voxel_size, not both")
     if bounds is None:
@@ -145,8 +171,11 @@ def fuse_model(model, cameras: Sequence, bg: torch.Tensor, *, resolution: Option
     truncation = truncation_voxels * voxel_size
     if bounds is None:
         lo, hi = [v - truncation for v in lo], [v + truncation for v in hi]
-    vol = TsdfVolume(lo, hi, voxel_size, truncation, device=model.get_xyz.device)
     table = camera_table(cameras)
+    if method == "poisson":
+        return _fuse_poisson(model, cameras, table, bg, lo, hi, voxel_size, alpha_min, batch, return_volume, depth, screen, poisson_iters,
+                             poisson_tol, sample_stride, spread, trim, info)
+    vol = TsdfVolume(lo, hi, voxel_size, truncation, device=model.get_xyz.device)
     if depth == "median":
         from .pixel_maps import plane_batches
         for idx, outs, raws in plane_batches(model, cameras, bg, ("median_depth",), batch=batch):
@@ -158,6 +187,32 @@ def fuse_model(model, cameras: Sequence, bg: torch.Tensor, *, resolution: Option
                           [o["render"] for o in outs], alpha_min=alpha_min)
     mesh = vol.extract(min_weight)
     return mesh + (vol,) if return_volume else mesh
+
+
+def _fuse_poisson(model, cameras, table, bg, lo, hi, voxel_size, alpha_min, batch, return_volume, depth, screen, iters, tol, stride, spread,
+                  trim, info):
+    from . import poisson
+    from .evaluate import _batches
+    parts = []
+    if depth == "median":
+        from .pixel_maps import plane_batches
+        for idx, outs, raws in plane_batches(model, cameras, bg, ("median_depth",), batch=batch):
+            parts.append(poisson.oriented_points(table[idx], [r["median_depth"] for r in raws], [o["rendered_alpha"] for o in outs],
+                                                 [o["render"] for o in outs], stride=stride, alpha_min=alpha_min, median=True))
+    else:
+        for idx, outs in _batches(model, cameras, bg, batch, full=True):
+            parts.append(poisson.oriented_points(table[idx], [o["rendered_depth"] for o in outs], [o["rendered_alpha"] for o in outs],
+                                                 [o["render"] for o in outs], stride=stride, alpha_min=alpha_min))
+    points, normals, weights, colours = (torch.cat([p[k] for p in parts]) for k in range(4))
+    vol = poisson.PoissonVolume(lo, hi, voxel_size, device=model.get_xyz.device)
+    vol.splat(points, normals, weights)
+    res = vol.solve(poisson.SCREEN if screen is None else screen, iters, poisson.TOL if tol is None else tol)
+    if info is not None:
+        info.update(res)
+    vertices, _, faces = vol.extract(trim, spread)
+    vcol = poisson.sample_colours(vertices, points, colours, max(2.0 * (spread + 1), 4.0) * voxel_size)
+    mesh = (vertices, vcol, faces)
+    return mesh + (vol.volume,) if return_volume else mesh
 
 
 # ---- PLY ---------------------------------------------------------------------------------------------------------------

@@ -1453,6 +1453,78 @@ int b3gs_gaussian_merge_emit(int32_t P, int32_t K, const float* positions, const
                              float* out_quaternions, float* out_opacities, float* out_features_dc, float* out_features_rest,
                              int32_t* cluster_of, int32_t* members, b3gs_stream_t stream);
 
+/* ---- screened Poisson surface reconstruction (added to ABI 18; csrc/poisson.hip, binocular3dgs_amd/poisson.py, INTEGRATION.md
+ * section 27) ---------------------------------------------------------------------------------------------------------------
+ * Eight entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * Oriented samples -> one smooth function over the node grid of a B3gsTsdfVolume (nodes at the voxel centres, x fastest) whose
+ * level set b3gs_mesh_count / b3gs_mesh_emit extract unchanged.  float32 unless stated, every statement ONE correctly rounded
+ * operation of + - * / sqrt in the order written (the library is built with -ffp-contract=off), one thread per output word,
+ * sums across threads as fixed-order fp64 folds: no floating-point atomic, no vendor library, and one result whatever the launch
+ * geometry.  tests/poisson_ref.py restates every statement in numpy; every output agrees bit for bit.
+ *
+ * 1. b3gs_oriented_points_batch / _emit: 1..8 views (B3gsTsdfView) of one W x H, W * H <= 2^27.  Pixel (px, py) of a view
+ *    qualifies when px % stride == 0 and py % stride == 0, 1 <= px <= W - 2, 1 <= py <= H - 2, and alpha >= alpha_min at the
+ *    pixel and at (px - 1, py), (px + 1, py), (px, py - 1), (px, py + 1).  z = depth / alpha at each of the five (the renderer's
+ *    mean depth, as b3gs_tsdf_integrate_batch defines it), or z = depth as given when `median` != 0.
+ *      rejected unless |z_n - z| <= rel_jump * z for the four neighbours n
+ *      P(q) = (((qx - (0.5 W - 0.5)) / fx) * z_q, ((qy - (0.5 H - 0.5)) / fy) * z_q, z_q)
+ *      a = P(px + 1, py) - P(px - 1, py);  b = P(px, py + 1) - P(px, py - 1);  n = b x a, n_0 = b_1 a_2 - b_2 a_1 and cyclic:
+ *      the side that faces the camera
+ *      |n| = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2), rejected unless > 0;  |P| likewise
+ *      c = (0 - ((n_0 P_0 + n_1 P_1) + n_2 P_2)) / (|n| |P|), rejected unless c > min_cos
+ *      u = n / |n|;  position_k = (rot[k] t_0 + rot[3 + k] t_1) + rot[6 + k] t_2 with t = P - trans (R^T (P - t));
+ *      normal_k likewise from u;  weight = c;  colour = the pixel's three colour words
+ *    The accepted pixels are compacted in (view, py, px) order.  batch leaves their number as ONE int64 at the start of the
+ *    workspace (b3gs_oriented_points_workspace_bytes, 0 for bad sizes; 256-byte aligned): the only word the host reads; emit,
+ *    with the same arguments and workspace, fills points [n, 3], normals [n, 3], weights [n], colours [n, 3] and writes nothing
+ *    past n rows.
+ * 2. b3gs_poisson_splat: per sample and axis a, c = (x_a - origin_a) / voxel - 0.5, base = floor(c), f = c - base.  A sample
+ *    whose base is outside 0 .. n_a - 2 on any axis (its 8 surrounding nodes are not all in the grid; NaN included) is dropped
+ *    and counted.  The others are sorted by the key (base_z ny + base_y) nx + base_x with the stable radix sort: the members of a
+ *    cell stay in sample order.  One thread per node visits its 8 cells (node - (dx, dy, dz)) for dz, dy, dx in {0, 1}, dx
+ *    fastest, and every member in order:  t_a = d_a ? f_a : 1 - f_a;  t = (t_x t_y) t_z;  in fp64 wt = w t (exact),
+ *    D = D + wt, V_a = V_a + wt n_a;  the four sums start at +0 and are rounded once to float32: density [n], vector [3, n].
+ * 3. b = 0 - 0.5 (((Vx(i+1) - Vx(i-1)) + (Vy(j+1) - Vy(j-1))) + (Vz(k+1) - Vz(k-1))), a value beyond the grid is 0.
+ *    A x = (((x_c - x(i-1)) + (x_c - x(i+1))) + ((x_c - x(j-1)) + (x_c - x(j+1)))) + ((x_c - x(k-1)) + (x_c - x(k+1)))
+ *          + (screen D_c) x_c, a neighbour beyond the grid is the node itself (Neumann).  b3gs_poisson_apply: out = A x.
+ *    A is symmetric positive definite when screen > 0 and some D > 0.
+ * 4. b3gs_poisson_solve: conjugate gradients from x = 0, r = p = b, `iters` iterations of TWO launches, no host read.
+ *    x, r, p, Ap are float32; a dot product u.v: q_i = (double)u_i (double)v_i (exact); one partial per 256 consecutive nodes
+ *    (missing nodes are +0): per 64 the xor butterfly 32, 16, .., 1, then (s_0 + s_1) + (s_2 + s_3); the partials are folded by
+ *    one wave: lane l adds l, l + 64, .. in order from +0, then the butterfly.  All of that in fp64.
+ *      rr = bb = b.b;  thr = (tol tol) bb (fp64);  done when rr <= thr or no sample survived the splat (status bit 0)
+ *      per iteration, unless done:  p = r + bf p (from the second iteration on);  pAp = p.Ap;  pAp == 0: done;
+ *        alpha = rr / pAp, af = (float)alpha;  x = x + af p;  r = r - af Ap;  rn = r.r;  beta = rn / rr, bf = (float)beta;
+ *        rr = rn;  iterations = iterations + 1;  done when rn <= thr
+ *    Once done, later launches return without writing.  The partial of a chunk of 256 nodes does not depend on the workgroup
+ *    that made it; the LAST workgroup of a launch to finish folds them (an arrival counter; nobody waits), so max_blocks (0: at
+ *    most 2048 workgroups, each walking chunks b, b + grid, ..) changes no bit.  Also written: rhs [n] = b.
+ *    The workspace begins with int64 words {dropped samples, samples, status, iterations, done} and the doubles {rr, bb}: the
+ *    caller reads them once.  screen <= 0 is B3GS_ERR_ARG.
+ * 5. b3gs_poisson_volume: iso = (float)(sum(D x) / sum(D)), the two sums as dot products above;  tsdf = x - iso (normals point
+ *    to free space: positive outside);  weight = D summed over the (2 spread + 1)^3 box of nodes clipped to the grid, one axis
+ *    after the other (x, y, z), each in index order from +0;  rgb = 0.
+ * workspace: b3gs_poisson_workspace_bytes(nx, ny, nz, nsamples) bytes (0 for bad sizes; about 32 bytes per node and 36 per
+ * sample), 256-byte aligned.  ORDER: b3gs_poisson_splat needs no initial content and writes the head words {dropped samples,
+ * samples}; b3gs_poisson_solve READS those two words (the status bit "no sample survived"), so it takes the workspace the splat
+ * of the same grid wrote, after it on the stream -- on any other bytes its status and stop flag are undefined.
+ * b3gs_poisson_volume reads nothing of the head and only uses the node arrays as scratch (the solver's state is lost).
+ * b3gs_poisson_apply takes no workspace. */
+size_t b3gs_oriented_points_workspace_bytes(int32_t nviews, int32_t W, int32_t H);
+int b3gs_oriented_points_batch(int32_t nviews, const B3gsTsdfView* views, int32_t W, int32_t H, int32_t stride, float alpha_min,
+                               float rel_jump, float min_cos, int32_t median, void* workspace, b3gs_stream_t stream);
+int b3gs_oriented_points_emit(int32_t nviews, const B3gsTsdfView* views, int32_t W, int32_t H, int32_t stride, float alpha_min,
+                              float rel_jump, float min_cos, int32_t median, void* workspace, int64_t npoints, float* points,
+                              float* normals, float* weights, float* colours, b3gs_stream_t stream);
+size_t b3gs_poisson_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t nsamples);
+int b3gs_poisson_splat(const B3gsTsdfVolume* grid, int64_t nsamples, const float* points, const float* normals, const float* weights,
+                       float* density, float* vector, void* workspace, b3gs_stream_t stream);
+int b3gs_poisson_apply(const B3gsTsdfVolume* grid, const float* density, float screen, const float* x, float* out, b3gs_stream_t stream);
+int b3gs_poisson_solve(const B3gsTsdfVolume* grid, const float* density, const float* vector, float screen, int32_t iters, float tol,
+                       int32_t max_blocks, float* rhs, float* x, void* workspace, b3gs_stream_t stream);
+int b3gs_poisson_volume(const B3gsTsdfVolume* volume, const float* density, const float* x, int32_t spread, void* workspace,
+                        b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
