@@ -162,6 +162,16 @@ class B3gsLabelRenderView(C.Structure):
                 ("label", C.c_void_p), ("weight", C.c_void_p)]
 
 
+class B3gsFeatureRenderView(C.Structure):
+    _fields_ = [("view", C.POINTER(B3gsScene)), ("geometry", C.c_void_p), ("binning", C.c_void_p), ("image", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
+class B3gsFeatureLiftView(C.Structure):
+    _fields_ = [("view", C.POINTER(B3gsScene)), ("geometry", C.c_void_p), ("binning", C.c_void_p), ("image", C.c_void_p),
+                ("maps", C.c_void_p), ("pixel_mask", C.c_void_p)]
+
+
 class B3gsContribOut(C.Structure):
     _fields_ = [("weight_q32", C.c_void_p), ("hits", C.c_void_p), ("wmax_bits", C.c_void_p), ("dominant", C.c_void_p)]
 
@@ -236,6 +246,8 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_blend_pixel_maps_batch",
            # added to ABI 18: segmentation from 2D label planes
            "b3gs_label_votes_batch", "b3gs_label_render_batch",
+           # added to ABI 18: feature fields
+           "b3gs_feature_render_batch", "b3gs_feature_lift_batch",
            # added to ABI 18: weighted k-means codebooks
            "b3gs_kmeans_workspace_bytes", "b3gs_kmeans_assign", "b3gs_kmeans",
            # added to ABI 18: undistorting a COLMAP dataset
@@ -459,6 +471,10 @@ def lib():
     L.b3gs_label_votes_batch.restype = C.c_int
     L.b3gs_label_render_batch.argtypes = [I32, C.POINTER(B3gsLabelRenderView), I32, V, V]
     L.b3gs_label_render_batch.restype = C.c_int
+    L.b3gs_feature_render_batch.argtypes = [I32, C.POINTER(B3gsFeatureRenderView), I32, V, V]
+    L.b3gs_feature_render_batch.restype = C.c_int
+    L.b3gs_feature_lift_batch.argtypes = [I32, C.POINTER(B3gsFeatureLiftView), I32, C.POINTER(C.c_float), V, V, V]
+    L.b3gs_feature_lift_batch.restype = C.c_int
     L.b3gs_kmeans_workspace_bytes.argtypes = [I32, I32, I32]
     L.b3gs_kmeans_workspace_bytes.restype = C.c_size_t
     L.b3gs_kmeans_assign.argtypes = [I32, I32, I32, V, V, V, V, V]

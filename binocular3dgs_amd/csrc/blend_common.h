@@ -1,5 +1,5 @@
 // Device functions shared by the kernels that walk a tile's list pixel by pixel: the blend (render.hip) and, through
-// tile_walk.h, the second walks (contrib.hip, pixelmaps.hip, segment.hip).  All of it is force-inlined: one workgroup -> tile
+// tile_walk.h, the second walks (contrib.hip, pixelmaps.hip, segment.hip, features.hip).  All of it is force-inlined: one workgroup -> tile
 // map, the two-segment tile list, the LDS staging with its quadrant cull and the exponent of the Gaussian, so that a second
 // walk of the lists takes every skip decision from the same instructions as the forward that wrote n_contrib.
 #pragma once

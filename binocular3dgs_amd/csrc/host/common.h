@@ -85,6 +85,7 @@ void bind_lpips(pybind11::module_& m);
 void bind_contrib(pybind11::module_& m);
 void bind_pixelmaps(pybind11::module_& m);
 void bind_segment(pybind11::module_& m);
+void bind_features(pybind11::module_& m);
 void bind_kmeans(pybind11::module_& m);
 void bind_undistort(pybind11::module_& m);
 void bind_edit(pybind11::module_& m);

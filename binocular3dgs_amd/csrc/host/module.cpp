@@ -63,6 +63,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_contrib(m);
   b3::bind_pixelmaps(m);
   b3::bind_segment(m);
+  b3::bind_features(m);
   b3::bind_kmeans(m);
   b3::bind_undistort(m);
   b3::bind_edit(m);

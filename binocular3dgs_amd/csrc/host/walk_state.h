@@ -1,5 +1,5 @@
 // The head of a view tuple of the calls that walk a finished forward's tile lists a second time (contrib.cpp, pixelmaps.cpp,
-// segment.cpp): (geometry, binning, image, ... W, H) -- the three uint8 state buffers a FusedRasterizer forward left in a slot
+// segment.cpp, features.cpp): (geometry, binning, image, ... W, H) -- the three uint8 state buffers a FusedRasterizer forward left in a slot
 // and the view's size.
 #pragma once
 #include "common.h"

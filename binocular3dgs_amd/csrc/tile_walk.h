@@ -1,5 +1,6 @@
 // The second walk of a finished forward's tile lists, stated once for the kernels that reduce it: contrib.hip (per Gaussian),
-// pixelmaps.hip (per pixel), segment.hip (votes per Gaussian and label, label render per pixel).
+// pixelmaps.hip (per pixel), segment.hip (votes per Gaussian and label, label render per pixel), features.hip (feature render per
+// pixel and channel, feature lift per Gaussian and channel).
 //
 // The walk is the forward's (render.hip): one 256-thread workgroup per 16x16 tile, one wave per 8x8 quadrant, the list staged
 // WALK_CHUNK entries at a time through LDS by the same stage_chunk() -- same quadrant cull -- and every entry evaluated with the

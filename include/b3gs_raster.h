@@ -1216,6 +1216,58 @@ int b3gs_label_votes_batch(int32_t nviews, const B3gsLabelVoteView* views, int32
 int b3gs_label_render_batch(int32_t nviews, const B3gsLabelRenderView* views, int32_t nlabels, const uint8_t* gaussian_label,
                             b3gs_stream_t stream);
 
+/* ---- feature fields (added to ABI 18; binocular3dgs_amd/features.py, csrc/features.hip) --------------------------
+ * The general continuous pair on the same second walk of a finished forward's tile lists (above: positions below the pixel's
+ * n_contrib, T restarted from 1, an entry blended exactly where the forward blended it, w = alpha * T with T the transmittance
+ * in front of the entry): a C-channel float field per Gaussian blended into [C, H, W] maps, and the adjoint that sums [C, H, W]
+ * maps back onto the Gaussians.  1 <= C <= B3GS_MAX_FEATURE_CHANNELS; channels are processed 8 at a time.
+ *
+ * b3gs_feature_render_batch: out[c][pixel] = the float32 sum, in list order, of w f[g][c] over the pixel's blended entries,
+ *   acc = fmaf(f, w, acc) from 0 -- the forward's statement of its colour planes; there is NO background term.
+ *   gaussian_features  float32 [P * C], row-major [P][C], shared by all views.
+ *   out                per view, float32 [C * H * W], required.  Every pixel inside W x H writes its C words (0 where nothing
+ *                      was blended): the planes need no initial content.  No atomics and no reduction across pixels: a view's
+ *                      planes are the same bits alone and at any position of a batch, and channel c of a call with C channels
+ *                      holds the bits of that channel rendered alone.
+ *
+ * b3gs_feature_lift_batch: sums_q32[g][c] += the sum over the blended (view, pixel, entry) of Gaussian g of
+ *   rint(float32(w * Fn) * 2^32),  Fn = min(1, max(-1, maps[c][pixel] / scale[c]))  (an IEEE float32 division).
+ *   maps        per view, float32 [C * H * W], required; finite values.
+ *   pixel_mask  per view, [H*W] bytes, nonzero = count the pixel; NULL = every pixel (b3gs_blend_contribution_batch's).
+ *   scale       float32 [C] in HOST memory, every entry finite and > 0 (checked: B3GS_ERR_ARG); it travels in the kernel
+ *               arguments.  |Fn| <= 1 keeps |w Fn| 2^32 below 2^32: choose scale[c] >= max |maps[c]| to lose nothing.
+ *   sums_q32    int64 [P * C], row-major [P][C], shared by all views and ACCUMULATED INTO (the caller zeroes it);
+ *               sum of w F = scale[c] * sums_q32[g][c] / 2^32.
+ *   weight_q32  uint64 [P] or NULL, accumulated into: the weight_q32 of b3gs_blend_contribution_batch under the same masks,
+ *               the same bits.  For maps[c] = scale[c] at the counted pixels, sums_q32[.][c] is that integer too.
+ *   The product w * Fn is exact to one float32 rounding and its scaling by 2^32 is exact; the conversion rounds to nearest,
+ *   ties to even.  Nothing but 64-bit integer adds reaches memory: the bits do not depend on the order of waves, tiles, views,
+ *   batches or calls.
+ *
+ * Both calls read geometry / binning / image and write only their outputs; neither reads anything back to the host.  All
+ * views share P (P == 0: nothing is done), sizes may differ.  1..8 views per call; arguments are checked before the first
+ * HIP call (B3GS_ERR_ARG). */
+#define B3GS_MAX_FEATURE_CHANNELS 256
+typedef struct B3gsFeatureRenderView {
+  const B3gsScene* view;         /* P, W, H are read */
+  const char* geometry;          /* as left by b3gs_forward_raw[_batch] + the blend forward of this view */
+  const char* binning;
+  const char* image;
+  float* out;                    /* [C*H*W] out */
+} B3gsFeatureRenderView;
+typedef struct B3gsFeatureLiftView {
+  const B3gsScene* view;         /* P, W, H are read */
+  const char* geometry;
+  const char* binning;
+  const char* image;
+  const float* maps;             /* [C*H*W] */
+  const uint8_t* pixel_mask;     /* [H*W], nonzero = count this pixel; NULL = every pixel */
+} B3gsFeatureLiftView;
+int b3gs_feature_render_batch(int32_t nviews, const B3gsFeatureRenderView* views, int32_t C, const float* gaussian_features,
+                              b3gs_stream_t stream);
+int b3gs_feature_lift_batch(int32_t nviews, const B3gsFeatureLiftView* views, int32_t C, const float* scale, int64_t* sums_q32,
+                            uint64_t* weight_q32, b3gs_stream_t stream);
+
 /* ---- weighted k-means codebooks (added to ABI 18; binocular3dgs_amd/compress.py, csrc/kmeans.hip) ---------------
  * Lloyd's algorithm over N rows x [N,D] (float32) with K codes [K,D] and optional row weights w [N] (float32, not negative;
  * NULL = 1), entirely on the stream: no host read.  1 <= D <= 64, 1 <= K <= 65536, N >= 0 (N == 0: returns B3GS_OK and does
