@@ -191,6 +191,16 @@ class B3gsSelect(C.Structure):
                    ("centre", C.c_double * 3), ("r2", C.c_double), ("cameras", C.c_void_p), ("masks", C.c_void_p)])
 
 
+class B3gsMcmcIO(C.Structure):
+    _fields_ = [("P", C.c_int32), ("P_old", C.c_int32), ("K", C.c_int32), ("n_max", C.c_int32), ("min_opacity", C.c_float),
+                ("offset", C.c_uint32), ("seed", C.c_uint64), ("param", C.c_void_p * 6), ("exp_avg", C.c_void_p * 6),
+                ("exp_avg_sq", C.c_void_p * 6), ("draws", C.c_void_p)]
+
+
+class B3gsMcmcViews(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("count", C.c_void_p), ("rank", C.c_void_p), ("weight_scan", C.c_void_p), ("head", C.c_void_p)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -261,7 +271,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_gaussian_merge_workspace_bytes", "b3gs_gaussian_merge_count", "b3gs_gaussian_merge_emit",
            # added to ABI 18: screened Poisson surface reconstruction
            "b3gs_oriented_points_workspace_bytes", "b3gs_oriented_points_batch", "b3gs_oriented_points_emit",
-           "b3gs_poisson_workspace_bytes", "b3gs_poisson_splat", "b3gs_poisson_apply", "b3gs_poisson_solve", "b3gs_poisson_volume")
+           "b3gs_poisson_workspace_bytes", "b3gs_poisson_splat", "b3gs_poisson_apply", "b3gs_poisson_solve", "b3gs_poisson_volume",
+           # added to ABI 18: fixed-budget training (MCMC relocation and position noise)
+           "b3gs_mcmc_random", "b3gs_mcmc_noise", "b3gs_mcmc_workspace_bytes", "b3gs_mcmc_relocate", "b3gs_mcmc_views")
 
 _lib = None
 
@@ -521,6 +533,16 @@ def lib():
     L.b3gs_poisson_solve.restype = C.c_int
     L.b3gs_poisson_volume.argtypes = [C.POINTER(B3gsTsdfVolume), V, V, I32, V, V]
     L.b3gs_poisson_volume.restype = C.c_int
+    L.b3gs_mcmc_random.argtypes = [I64, C.c_uint64, C.c_uint32, C.c_uint32, I32, V, V]
+    L.b3gs_mcmc_random.restype = C.c_int
+    L.b3gs_mcmc_noise.argtypes = [I32, V, V, V, V, V, C.c_uint64, C.c_uint32, F, F, V, V]
+    L.b3gs_mcmc_noise.restype = C.c_int
+    L.b3gs_mcmc_workspace_bytes.argtypes = [I32]
+    L.b3gs_mcmc_workspace_bytes.restype = C.c_size_t
+    L.b3gs_mcmc_relocate.argtypes = [C.POINTER(B3gsMcmcIO), V, V]
+    L.b3gs_mcmc_relocate.restype = C.c_int
+    L.b3gs_mcmc_views.argtypes = [I32, V, C.POINTER(B3gsMcmcViews)]
+    L.b3gs_mcmc_views.restype = C.c_int
     L.b3gs_pose_gradient_workspace_bytes.argtypes = [I32, I32]
     L.b3gs_pose_gradient_workspace_bytes.restype = C.c_size_t
     L.b3gs_pose_gradient.argtypes = [I32, I32, I32, V, V, V, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

@@ -92,5 +92,6 @@ void bind_edit(pybind11::module_& m);
 void bind_pose(pybind11::module_& m);
 void bind_lod(pybind11::module_& m);
 void bind_poisson(pybind11::module_& m);
+void bind_mcmc(pybind11::module_& m);
 
 }  // namespace b3

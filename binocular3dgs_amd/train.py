@@ -11,6 +11,8 @@ The reference's train.py: a COLMAP / Blender dataset folder in, a trained model 
     --test_iterations      evaluate.training_report's "[ITER n] Evaluating test|train: L1 .. PSNR .." lines
     --save_iterations      <model_path>/point_cloud/iteration_<n>/point_cloud.ply (before the optimiser step, as there)
     --checkpoint_iterations / --start_checkpoint   <model_path>/chkpnt<n>.pth (checkpoint.py: the reference's tuple)
+    --densify adc|mcmc     adc (default): the reference's clone / split / prune; mcmc: mcmc.McmcSchedule -- relocation, growth to
+                           --cap_max and position noise (--noise_lr, --opacity_reg, --scale_reg); --step schedule only
 
 <model_path>/cfg_args holds the Namespace(...) line the reference writes; `python -m binocular3dgs_amd.spiral -m MODEL_PATH`
 and evaluate.write_results read the result without further arguments.  No progress bar, no tensorboard, no network GUI.
@@ -78,7 +80,25 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--step", choices=("schedule", "graph"), default="schedule",
                    help='"schedule": the reference-shaped loop, one launch per statement (schedule.IterationSchedule); "graph": '
                         'the same iteration on the fused step, one HIP-graph replay per iteration (graph_trainer.GraphTrainer)')
+    p.add_argument("--densify", choices=("adc", "mcmc"), default="adc",
+                   help='"adc": clone / split / prune by the gradient threshold (the reference\'s rule); "mcmc": relocation, growth '
+                        'to --cap_max and position noise (mcmc.McmcSchedule)')
+    p.add_argument("--cap_max", type=int, default=None, help="--densify mcmc: the final number of Gaussians")
+    p.add_argument("--noise_lr", type=float, default=5e5)
+    p.add_argument("--opacity_reg", type=float, default=0.01)
+    p.add_argument("--scale_reg", type=float, default=0.01)
     return p
+
+
+def check_args(args) -> None:
+    """The rules between the flags; ValueError with the reason."""
+    if getattr(args, "densify", "adc") != "mcmc":
+        return
+    if getattr(args, "cap_max", None) is None or args.cap_max < 1:
+        raise ValueError("--densify mcmc requires --cap_max N, the final number of Gaussians (N >= 1)")
+    if getattr(args, "step", "schedule") == "graph":
+        raise ValueError("--densify mcmc --step graph is not supported: the noise launch and the regulariser are not part of "
+                         "the captured step yet; use --step schedule")
 
 
 def cfg_args_text(args) -> str:
@@ -95,6 +115,7 @@ def run(args) -> dict:
     from .scene import Scene
     from .schedule import IterationSchedule
     args = argparse.Namespace(**vars(args))
+    check_args(args)
     say = (lambda *a, **k: None) if args.quiet else print
     args.source_path = os.path.abspath(args.source_path)
     args.save_iterations = list(args.save_iterations) + [args.iterations]
@@ -140,6 +161,10 @@ def run(args) -> dict:
         from .graph_trainer import GraphTrainer
         sched = GraphTrainer(model, scene, PipelineParams(), background, save_iterations=args.save_iterations,
                              checkpoint_iterations=args.checkpoint_iterations, **kw)
+    elif getattr(args, "densify", "adc") == "mcmc":
+        from .mcmc import McmcSchedule
+        sched = McmcSchedule(model, scene, PipelineParams(), background, cap_max=args.cap_max, seed=args.seed, noise_lr=args.noise_lr,
+                             opacity_reg=args.opacity_reg, scale_reg=args.scale_reg, **kw)
     else:
         sched = IterationSchedule(model, scene, PipelineParams(), background, **kw)
     reports = sched.reports
@@ -165,7 +190,12 @@ def run(args) -> dict:
 
 
 def main(argv=None) -> int:
-    args = parser().parse_args(argv)
+    p = parser()
+    args = p.parse_args(argv)
+    try:
+        check_args(args)
+    except ValueError as e:
+        p.error(str(e))
     say = (lambda *a: None) if args.quiet else print
     say("Optimizing " + args.model_path)
     run(args)

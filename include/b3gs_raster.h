@@ -1577,6 +1577,79 @@ int b3gs_poisson_solve(const B3gsTsdfVolume* grid, const float* density, const f
 int b3gs_poisson_volume(const B3gsTsdfVolume* volume, const float* density, const float* x, int32_t spread, void* workspace,
                         b3gs_stream_t stream);
 
+/* ---- fixed-budget training: MCMC relocation and position noise (added to ABI 18; csrc/mcmc.hip, binocular3dgs_amd/mcmc.py,
+ * INTEGRATION.md section 29) ------------------------------------------------------------------------------------------------
+ * Five entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * tests/mcmc_ref.py restates every rule below in numpy / Python integers.
+ *
+ * 1. Random numbers: Philox4x32-10 (Salmon et al., SC 2011).  One round of counter c[4] under key k[2]:
+ *      p0 = 0xD2511F53 * c[0], p1 = 0xCD9E8D57 * c[2]  (64-bit products)
+ *      c = { hi(p1) ^ c[1] ^ k[0], lo(p1), hi(p0) ^ c[3] ^ k[1], lo(p0) };  ten rounds, and between two rounds
+ *      k[0] += 0x9E3779B9, k[1] += 0xBB67AE85.
+ *    The key is the 64-bit seed (k[0] its low word), the counter is (index, offset, stream_id, 0); one counter gives one BLOCK
+ *    of four words w0..w3.
+ *      B3GS_RANDOM_U32     element e of the output is word e % 4 of the block with index e / 4
+ *      B3GS_RANDOM_NORMAL  element e (float32) comes from the block with index e / 4 and its word pair (w0, w1) when
+ *                          e % 4 < 2, else (w2, w3); with (a, b) that pair, in fp64: u1 = (a + 0.5) 2^-32, u2 = (b + 0.5) 2^-32,
+ *                          r = sqrt(-2 log(u1)); an even e takes r cos(2 pi u2), an odd e r sin(2 pi u2), rounded ONCE to float32
+ *                          (u1 > 0: the logarithm is finite)
+ *      a 64-bit draw       (relocation) of index j is w0 | w1 << 32 of the block with index j
+ *    b3gs_mcmc_random fills out[n] (0 <= n <= 2^32) with uint32 or float32 words.
+ * 2. b3gs_mcmc_noise: per row i of the raw parameters, in float32, every statement one rounded operation in the order written:
+ *      q = rotation_i / sqrt(((w w + x x) + y y) + z z);  R the rotation matrix of q as build_rotation states it;
+ *      v_k = exp(scaling_ik)^2;  t_k = ((R_0k n_0 + R_1k n_1) + R_2k n_2) v_k;  d_j = (R_j0 t_0 + R_j1 t_1) + R_j2 t_2  (= Sigma n)
+ *      o = 1 / (1 + exp(-opacity_i));  g = 1 / (1 + exp(100 (o - 0.005)));  xyz_ij = xyz_ij + (d_j g) (noise_lr lr_xyz)
+ *    n = normals[3 i + k] when `normals` is given, else element 3 i + k of B3GS_RANDOM_NORMAL for (seed, stream_id 0,
+ *    offset = iteration), made in registers.  lr_xyz_dev (one float on the device) replaces lr_xyz when it is not NULL.
+ *    No atomics, no row reads another row.
+ * 3. b3gs_mcmc_relocate, in place on the six raw parameter tensors of P rows (rows [P_old, P) are the APPENDED ones of a growth
+ *    step, P_old == P: none).  No host read; `workspace` holds b3gs_mcmc_workspace_bytes(P) bytes (0 for bad sizes), 256-byte
+ *    aligned, no initial content.
+ *      classify  o_i = 1 / (1 + exp(-(double)opacity_i)) in fp64.  Row i is DEAD when o_i <= (double)min_opacity or i >= P_old;
+ *                its weight is q_i = dead ? 0 : (uint32)(o_i 2^24).
+ *      scans     rank_i = the dead rows in front of i;  W_i = q_0 + .. + q_i as uint64;  total = W_(P-1).
+ *      sample    the dead row of rank j takes the 64-bit draw u of (seed, stream_id 1, offset, index j) -- or draws[j] when
+ *                `draws` is given -- and t = (u * total) >> 64; src_i = the first row s with W_s > t (alive, never a zero-weight
+ *                row); count_s += 1.  total == 0: nothing is written at all and bit 0 of the status word is set.
+ *      correct   every alive row with count > 0, in fp64, each statement one operation in the order written:
+ *                N = min(count + 1, n_max);  o' = 1 - pow(1 - o, 1 / N);  p_1 = o', p_(k+1) = p_k o';
+ *                denom = sum over i = 1..N, inside it k = 0..i-1, of +- (C(i-1, k) p_(k+1)) / sqrt(k + 1), added for even k and
+ *                subtracted for odd k, from +0;  for each axis s' = (exp((double)scaling) o) / denom;
+ *                o' clamped to [min_opacity, 1 - 2^-24];  stored (float)log(o' / (1 - o')) and (float)log(s').
+ *      apply     a dead row with a source copies xyz, rotation, features_dc and features_rest from it bit for bit and takes the
+ *                source's corrected opacity and scaling; the source takes them too.  The Adam moments (when given: all twelve
+ *                pointers of exp_avg / exp_avg_sq, or none) of every row WRITTEN, sources and destinations, become zero.
+ *    b3gs_mcmc_views: where src (int32 [P], -1: not relocated), count (int32 [P]), rank (int32 [P]), W (uint64 [P]) and the head
+ *    words (int64: total, dead rows, status) of the last call lie inside the workspace. */
+#define B3GS_RANDOM_U32 0
+#define B3GS_RANDOM_NORMAL 1
+#define B3GS_MCMC_MAX_N 51
+typedef struct B3gsMcmcIO {
+  int32_t P, P_old;
+  int32_t K;                 /* floats of one features_rest row (0: none; features_dc rows hold 3) */
+  int32_t n_max;             /* 1 .. B3GS_MCMC_MAX_N */
+  float min_opacity;         /* in (0, 1) */
+  uint32_t offset;
+  uint64_t seed;
+  float* param[6];           /* xyz, features_dc, features_rest, scaling, rotation, opacity */
+  float* exp_avg[6];
+  float* exp_avg_sq[6];
+  const uint64_t* draws;     /* NULL, or [P] injected draws by dead rank (tests) */
+} B3gsMcmcIO;
+typedef struct B3gsMcmcViews {
+  const int32_t* src;
+  const int32_t* count;
+  const int32_t* rank;
+  const uint64_t* weight_scan;
+  const int64_t* head;       /* [3] total weight, dead rows, status (bit 0: nothing alive, no-op) */
+} B3gsMcmcViews;
+int b3gs_mcmc_random(int64_t n, uint64_t seed, uint32_t stream_id, uint32_t offset, int32_t kind, void* out, b3gs_stream_t stream);
+int b3gs_mcmc_noise(int32_t P, const float* scaling, const float* rotation, const float* opacity, float* xyz, const float* normals,
+                    uint64_t seed, uint32_t iteration, float noise_lr, float lr_xyz, const float* lr_xyz_dev, b3gs_stream_t stream);
+size_t b3gs_mcmc_workspace_bytes(int32_t P);
+int b3gs_mcmc_relocate(const B3gsMcmcIO* io, void* workspace, b3gs_stream_t stream);
+int b3gs_mcmc_views(int32_t P, void* workspace, B3gsMcmcViews* out);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
