@@ -201,6 +201,18 @@ class B3gsMcmcViews(C.Structure):
     _fields_ = [("src", C.c_void_p), ("count", C.c_void_p), ("rank", C.c_void_p), ("weight_scan", C.c_void_p), ("head", C.c_void_p)]
 
 
+class B3gsDepthPriorIO(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("depth", C.c_void_p), ("alpha", C.c_void_p), ("prior", C.c_void_p),
+                ("mask", C.c_void_p), ("mode", C.c_int32), ("patch", C.c_int32), ("min_valid", C.c_int32), ("alpha_min", C.c_float),
+                ("w_global", C.c_double), ("w_local", C.c_double), ("offset_dev", C.c_void_p), ("dL_ddepth", C.c_void_p),
+                ("parts", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+class B3gsDepthResizeIO(C.Structure):
+    _fields_ = [("Wsrc", C.c_int32), ("Hsrc", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("src", C.c_void_p),
+                ("src_mask", C.c_void_p), ("prior", C.c_void_p), ("mask", C.c_void_p)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -273,7 +285,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            "b3gs_oriented_points_workspace_bytes", "b3gs_oriented_points_batch", "b3gs_oriented_points_emit",
            "b3gs_poisson_workspace_bytes", "b3gs_poisson_splat", "b3gs_poisson_apply", "b3gs_poisson_solve", "b3gs_poisson_volume",
            # added to ABI 18: fixed-budget training (MCMC relocation and position noise)
-           "b3gs_mcmc_random", "b3gs_mcmc_noise", "b3gs_mcmc_workspace_bytes", "b3gs_mcmc_relocate", "b3gs_mcmc_views")
+           "b3gs_mcmc_random", "b3gs_mcmc_noise", "b3gs_mcmc_workspace_bytes", "b3gs_mcmc_relocate", "b3gs_mcmc_views",
+           # added to ABI 18: depth priors (Pearson depth loss, prior resize)
+           "b3gs_depth_prior_workspace_bytes", "b3gs_depth_prior_loss_batch", "b3gs_resize_depth_batch")
 
 _lib = None
 
@@ -543,6 +557,12 @@ def lib():
     L.b3gs_mcmc_relocate.restype = C.c_int
     L.b3gs_mcmc_views.argtypes = [I32, V, C.POINTER(B3gsMcmcViews)]
     L.b3gs_mcmc_views.restype = C.c_int
+    L.b3gs_depth_prior_workspace_bytes.argtypes = [I32, I32, I32]
+    L.b3gs_depth_prior_workspace_bytes.restype = C.c_size_t
+    L.b3gs_depth_prior_loss_batch.argtypes = [I32, C.POINTER(B3gsDepthPriorIO), V]
+    L.b3gs_depth_prior_loss_batch.restype = C.c_int
+    L.b3gs_resize_depth_batch.argtypes = [I32, C.POINTER(B3gsDepthResizeIO), V]
+    L.b3gs_resize_depth_batch.restype = C.c_int
     L.b3gs_pose_gradient_workspace_bytes.argtypes = [I32, I32]
     L.b3gs_pose_gradient_workspace_bytes.restype = C.c_size_t
     L.b3gs_pose_gradient.argtypes = [I32, I32, I32, V, V, V, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

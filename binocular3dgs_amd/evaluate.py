@@ -232,21 +232,36 @@ def training_report(model, test_cameras, train_cameras, bg: torch.Tensor, *, bat
     return res
 
 
+def depth_pearson(model, cameras: Sequence, bg: torch.Tensor, priors_dir: str, mode: str = "depth") -> List[float]:
+    """rho_image of depth_prior.depth_prior_loss between every camera's rendered depth and <priors_dir>/<image_name>.npy
+    (resized to the camera's size; every valid pixel is used).  One host read per view, behind the loop."""
+    from .depth_prior import depth_prior_loss, load_priors
+    from .render import PipelineParams, render
+    priors = load_priors(priors_dir, cameras, device=bg.device)
+    rhos = []
+    with torch.no_grad():
+        for k, (cam, (prior, mask)) in enumerate(zip(cameras, priors)):
+            pkg = render(cam, model, PipelineParams(), bg)
+            _, parts = depth_prior_loss(pkg["rendered_depth"], pkg["rendered_alpha"], prior, mask, mode=mode, return_parts=True)
+            rhos.append(parts[5])
+    return [float(x) for x in torch.stack(rhos).cpu()] if rhos else []
+
+
 # ---- results.json / per_view.json (metrics.py:105-122) ----------------------------------------------------------------
 def write_results(model_path: str, method: str, per_view: Sequence[dict], names: Sequence[str], aligned: Optional[Sequence[dict]] = None,
                   twists=None) -> dict:
     """Writes <model_path>/results.json {method: {"SSIM", "PSNR"}} and per_view.json {method: {"SSIM": {name: v}, "PSNR":
     {name: v}}} in the reference's layout (json.dump, indent=True); the "LPIPS" key is written in both files, as
-    metrics.py:112-117 does, when EVERY per-view entry carries it, and left out otherwise.  Means are fp32, as
+    metrics.py:112-117 does, when EVERY per-view entry carries it, and left out otherwise; so is "DepthPearson" (depth_pearson).  Means are fp32, as
     torch.tensor(values).mean() is there.  `aligned` (the per-view metrics after pose alignment) adds the same keys with the
     suffix _aligned behind them, `twists` ([n,6]) adds per_view.json's "twist": {name: [omega, t]}; without them the files are
     what they were.  Returns the two dicts."""
     if len(per_view) != len(names) or (aligned is not None and len(aligned) != len(names)):
         raise ValueError("one name per view")
-    keys = ("SSIM", "PSNR") + (("LPIPS",) if per_view and all("LPIPS" in v for v in per_view) else ())
+    keys = ("SSIM", "PSNR") + tuple(k for k in ("LPIPS", "DepthPearson") if per_view and all(k in v for v in per_view))
     vals = {k: torch.tensor([float(v[k]) for v in per_view]) for k in keys}
     if aligned is not None:
-        vals.update({k + "_aligned": torch.tensor([float(v[k]) for v in aligned]) for k in keys})
+        vals.update({k + "_aligned": torch.tensor([float(v[k]) for v in aligned]) for k in keys if all(k in v for v in aligned)})
     full = {method: {k: vals[k].mean().item() for k in vals}}
     per = {method: {k: {name: x for x, name in zip(vals[k].tolist(), names)} for k in vals}}
     if twists is not None:
@@ -261,12 +276,15 @@ def write_results(model_path: str, method: str, per_view: Sequence[dict], names:
 
 # ---- command line: metrics.py over the test cameras of a trained model ------------------------------------------------
 def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1, mode: str = "png", lpips_weights=None,
-        masks=None, align_poses: int = 0, align_scales: Sequence[int] = (4, 2, 1)) -> dict:
+        masks=None, align_poses: int = 0, align_scales: Sequence[int] = (4, 2, 1), depth_priors: Optional[str] = None,
+        depth_prior_mode: Optional[str] = None) -> dict:
     """Loads <model_path>/point_cloud/iteration_<it> and the dataset's test cameras (cfg_args gives the defaults, as in
     spiral.py), evaluates them, prints the means in metrics.py:107-109's format and writes results.json / per_view.json under
     method ours_<it>.  `masks`: DTU IDR object masks per test camera (the command line does not read them).
     align_poses = N > 0: the cameras are refined for N iterations each (pose.refine_poses, coarse to fine over align_scales)
-    and evaluated again; the result gains "aligned" (evaluate_views of the refined cameras) and "twists"."""
+    and evaluated again; the result gains "aligned" (evaluate_views of the refined cameras) and "twists".
+    depth_priors = DIR: "DepthPearson", the mean rho_image against <DIR>/<image_name>.npy of the test views (depth_pearson;
+    depth_prior_mode defaults to the run's own in cfg_args), in results.json and per view in per_view.json."""
     from .gaussian_model import GaussianModel
     from .scene import Scene
     from .spiral import max_iteration, read_cfg_args
@@ -291,6 +309,12 @@ def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1,
     print("  PSNR : {:>12.7f}".format(res["PSNR"]))
     if "LPIPS" in res:
         print("  LPIPS: {:>12.7f}".format(res["LPIPS"]))
+    if depth_priors:
+        rhos = depth_pearson(model, cams, bg, depth_priors, depth_prior_mode or cfg.get("depth_prior_mode", "depth") or "depth")
+        for v, r in zip(res["per_view"], rhos):
+            v["DepthPearson"] = r
+        res["DepthPearson"] = float(torch.tensor(rhos).mean())
+        print("  DepthPearson: {:>12.7f}".format(res["DepthPearson"]))
     print("")
     names = ["{0:05d}.png".format(i) for i in range(len(cams))]      # render.py:34: the file names metrics.py lists
     if align_poses > 0:
@@ -322,6 +346,9 @@ def main(argv=None) -> int:
     p.add_argument("--align_poses", type=int, default=0, metavar="N",
                    help="align every held-out camera to the model by N photometric pose steps before scoring it again")
     p.add_argument("--align_scales", type=int, nargs="+", default=[4, 2, 1], help="the coarse-to-fine pyramid of the alignment")
+    p.add_argument("--depth_priors", default=None, metavar="DIR",
+                   help="<image_name>.npy priors of the test views: adds DepthPearson (mean rho_image) to results.json / per_view.json")
+    p.add_argument("--depth_prior_mode", choices=("depth", "disparity"), default=None, help="default: the training run's")
     a = p.parse_args(argv)
     w = None
     if a.lpips_npz:
@@ -334,7 +361,8 @@ def main(argv=None) -> int:
             p.error("--lpips_vgg and --lpips_lin go together")
         from .lpips import load_weights
         w = load_weights(a.lpips_vgg, a.lpips_lin)
-    run(a.model_path, a.source_path, a.iteration, a.mode, w, align_poses=a.align_poses, align_scales=a.align_scales)
+    run(a.model_path, a.source_path, a.iteration, a.mode, w, align_poses=a.align_poses, align_scales=a.align_scales,
+        depth_priors=a.depth_priors, depth_prior_mode=a.depth_prior_mode)
     return 0
 
 

@@ -9,12 +9,16 @@ What a captured graph fixes, and where each per-iteration value therefore lives
     the shift                                CameraPairSlots.trans_dist_dev (B3gsLossIO::trans_dist_dev)
     the ground-truth image, the mask         copied into static buffers (the mask: gt_alpha_mask, else bg_mask, schedule.py:95-98)
     the background colour                    three floats of a static block (refreshed when the caller hands in another tensor)
+    the depth prior, its validity, the       copied into static buffers next to the mask; the patch offsets: two int32 words
+    patch offsets (depth_prior.PriorTerm)    (PriorTerm.offset_buffer) the kernels read, one pinned upload per draw
     the learning rates                       six floats of the same block (B3gsAdamSegment::lr_dev), one pinned upload
 No value is read back inside an iteration.
 
 What cannot live in device memory is a SHAPE of the graph, captured at its first use and kept:
-    (pair?, opacity decay factor of the Adam launch or 0, statistics on?, mask kind)
+    (pair?, opacity decay factor of the Adam launch or 0, statistics on?, mask kind[, "prior"])
 -- single view while `it <= shift_cam_start` or `binocular` is off, the (input, shifted) pair with one depth sort afterwards;
+the fifth entry is there while the depth-prior term is active (all training views carry a prior, or none: a mixed set is
+refused) and ABSENT otherwise, so a run without priors has the keys, the events and the launches it always had;
 the decay switches on once (`it > densify_from_iter`), the statistics switch off once (`it >= densify_until_iter`, only with
 the decay off: with it on, densification runs to the end, schedule.py:119-120).  Every kept graph is dropped, and captured
 again at its next use, exactly when an address or a launch argument changed: after densify_and_prune (P), after
@@ -52,7 +56,7 @@ import gc
 
 import torch
 
-Draw = collections.namedtuple("Draw", "it view shift bg lr key full")
+Draw = collections.namedtuple("Draw", "it view shift bg lr key full offset", defaults=(None,))
 
 
 class _Captured:
@@ -68,7 +72,7 @@ class _Captured:
 class FusedBackend:
     """The device side of GraphTrainer: static storage, the step objects, capture and the capacity word."""
 
-    def __init__(self, model, views, background, lambda_dssim=0.2, smooth_weight=0.05, binning_capacity=None):
+    def __init__(self, model, views, background, lambda_dssim=0.2, smooth_weight=0.05, binning_capacity=None, depth_prior=None):
         from . import _lib, checkpoint
         from .camera import CameraPairSlots, _PinnedRing
         from .fused import FusedRasterizer
@@ -105,6 +109,17 @@ class FusedBackend:
         self.slots = CameraPairSlots(v0, 0.1)
         self.gt = v0.original_image.to(dev, torch.float32).clone()
         self.mask = torch.zeros((1, H, W), dtype=torch.float32, device=dev)
+        # depth_prior.PriorTerm: static prior plane, validity and offset words; every training view carries a prior, or none
+        self.prior_term = depth_prior if (depth_prior is not None and depth_prior.enabled) else None
+        self.has_prior = False
+        if self.prior_term is not None:
+            from .depth_prior import check_prior_set
+            self.has_prior = check_prior_set(self.views)
+        if self.has_prior:
+            self.prior = torch.zeros((1, H, W), dtype=torch.float32, device=dev)
+            self.prior_mask = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
+            self.offset_dev = self.prior_term.offset_buffer(dev)
+        self._prior = False
         self.fused = FusedRasterizer(model, W, H, num_slots=2, want_means2D=False, binning_capacity=binning_capacity)
         self.st = ViewShardedStep(model, [(self.slots.cam, self.slots.shifted, 0.1)], self.bg, optimizer=self.opt,
                                   fused=self.fused, overflow_check_every=0)
@@ -131,6 +146,10 @@ class FusedBackend:
         kind = d.key[3]
         if kind is not None:
             self.mask.copy_(cam.gt_alpha_mask if kind == "alpha" else cam.bg_mask, non_blocking=True)
+        if len(d.key) > 4:
+            self.prior.copy_(cam.depth_prior, non_blocking=True)
+            self.prior_mask.copy_(cam.depth_prior_mask, non_blocking=True)
+            self.prior_term.upload_offset(d.offset, self.offset_dev.device)
         if d.bg is not self._bg_src:
             self.bg.copy_(d.bg, non_blocking=True)
             self._bg_src = d.bg
@@ -142,7 +161,8 @@ class FusedBackend:
         self._ring.uploaded(k, self.lr_dev.device)
 
     def _configure(self, key):
-        pair, decay, stats, kind = key
+        pair, decay, stats, kind = key[:4]
+        self._prior = len(key) > 4
         v0, v1 = self._both
         self.st.views = [v0, v1] if pair else [v0]
         v0.mate = 1 if pair else None
@@ -160,6 +180,8 @@ class FusedBackend:
                                      gt_alpha_mask=self.mask if kind == "alpha" else None,
                                      bg_mask=self.mask if kind == "bg" else None, lambda_smooth=self.smooth_weight,
                                      slot=0, unit_grad=True)
+        if self._prior:
+            total = total + self.prior_term.loss(cam, pkg, offset_dev=self.offset_dev, prior=self.prior, mask=self.prior_mask)
         self._loss = total.detach()
         return total
 
@@ -239,7 +261,7 @@ class GraphTrainer:
                  densify_until_iter=15_000, densification_interval=100, densify_grad_threshold=0.0002, min_opacity=0.005,
                  sh_interval=1000, smooth_weight=0.05, log_item=False, before_densify=None, test_cameras=None,
                  test_iterations=(), report_fn=None, after_report=None, save_iterations=(), checkpoint_iterations=(),
-                 check_every=32, binning_capacity=None, backend=None, events=None):
+                 check_every=32, binning_capacity=None, backend=None, events=None, depth_prior=None):
         if ops is not None or log_item:
             raise ValueError("GraphTrainer runs the fused step: `ops` and `log_item` belong to IterationSchedule")
         self.model, self.scene, self.pipe, self.background = model, scene, pipe, background
@@ -255,7 +277,8 @@ class GraphTrainer:
         self.views = list(scene.getTrainCameras())
         self.check_every = int(check_every)
         self.backend = backend if backend is not None else FusedBackend(model, self.views, background, lambda_dssim,
-                                                                        smooth_weight, binning_capacity)
+                                                                        smooth_weight, binning_capacity, depth_prior)
+        self.depth_prior = depth_prior
         self.events = events
         self.densified = False
         self.captures = 0        # graphs captured so far: a replay does not move it
@@ -346,7 +369,10 @@ class GraphTrainer:
             self.after_report(it)
             self._ev("after_report", it=it)
         key = (pair, float(self.decay) if (decay_on and adam) else 0.0, bool(stats), b.mask_kind(view_index))
-        self._run(Draw(it, view_index, float(shift) if pair else None, self.background, lr, key, adam))
+        offset = None
+        if getattr(b, "has_prior", False) and self.depth_prior.active(it):
+            key, offset = key + ("prior",), self.depth_prior.draw_offset()      # (the term's own generator; kept for a repeat)
+        self._run(Draw(it, view_index, float(shift) if pair else None, self.background, lr, key, adam, offset))
         self.densified = False
         if not adam:
             self.settle()                                   # before a densification; and no run ends on a raised word

@@ -163,6 +163,8 @@ class McmcSchedule(IterationSchedule):
         recon = (1.0 - self.lam) * photo + self.lam * (1.0 - ops.ssim(first["render"], target))
         reg = self.opacity_reg * m.get_opacity.mean() + self.scale_reg * m.get_scaling.mean()
         total = recon + stereo + coverage + reg
+        if self.depth_prior is not None:
+            total = self.depth_prior.add(total, it, cam, first)
         total.backward()
         self.densified = False
         with torch.no_grad():

@@ -35,7 +35,7 @@ class Scene:
     @classmethod
     def from_dataset(cls, source_path: str, model, *, images="images", eval=True, n_views=3, dataset_name="LLFF", suffix=None,
                      resolution=-1, white_background=False, init_points="matcher", model_path=None, shuffle=True,
-                     load_iteration=None, device="cuda"):
+                     load_iteration=None, device="cuda", depth_priors=None):
         """scene/__init__.py:26-84.  `model`: a GaussianModel (filled from the initial points, or from
         <model_path>/point_cloud/iteration_<load_iteration>, -1 = the latest) or None (cameras only)."""
         import json
@@ -65,6 +65,10 @@ class Scene:
         scene = cls(_load_cameras(train, resolution, white_background, thr, device), model,
                     _load_cameras(test, resolution, white_background, thr, device), info.radius, model_path or "")
         scene.loaded_iter, scene.scene_info = loaded, info
+        if depth_priors:
+            # <depth_priors>/<image_name>.npy of every TRAINING view -> Camera.depth_prior / depth_prior_mask at its size
+            from .depth_prior import attach_priors
+            attach_priors(depth_priors, scene.getTrainCameras(), device=device)
         if model is not None:
             if loaded:
                 model.load_ply(os.path.join(model_path, "point_cloud", "iteration_" + str(loaded), "point_cloud.ply"))

@@ -41,7 +41,7 @@ class IterationSchedule:
                  binocular=True, opacity_decay_factor=0.995, lambda_dssim=0.2, densify_from_iter=500,
                  densify_until_iter=15_000, densification_interval=100, densify_grad_threshold=0.0002, min_opacity=0.005,
                  sh_interval=1000, smooth_weight=0.05, log_item=False, before_densify=None, test_cameras=None,
-                 test_iterations=(), report_fn=None, after_report=None):
+                 test_iterations=(), report_fn=None, after_report=None, depth_prior=None):
         self.model, self.scene, self.pipe, self.background = model, scene, pipe, background
         self.ops = ops if ops is not None else default_ops()
         self.iterations, self.shift_cam_start, self.binocular = iterations, shift_cam_start, binocular
@@ -53,6 +53,8 @@ class IterationSchedule:
         # train.py:166 training_report: {iteration: {"test": (l1, psnr), "train": (l1, psnr)}} for every iteration listed
         self.test_cameras, self.test_iterations = list(test_cameras or []), frozenset(test_iterations)
         self.report_fn, self.reports = report_fn, {}
+        # depth_prior.PriorTerm or None: a view that carries a `depth_prior` adds the Pearson depth term to the total
+        self.depth_prior = depth_prior
         self.after_report = after_report    # called with the iteration at train.py:166-169 (the point where it saves)
         self.views = list(scene.getTrainCameras())
         H, W = self.views[0].image_height, self.views[0].image_width
@@ -99,6 +101,8 @@ class IterationSchedule:
         photo = ops.l1_loss(first["render"], target)
         recon = (1.0 - self.lam) * photo + self.lam * (1.0 - ops.ssim(first["render"], target))
         total = recon + stereo + coverage
+        if self.depth_prior is not None:
+            total = self.depth_prior.add(total, it, cam, first)
         total.backward()
         self.densified = False
         with torch.no_grad():

@@ -11,6 +11,9 @@ The reference's train.py: a COLMAP / Blender dataset folder in, a trained model 
     --test_iterations      evaluate.training_report's "[ITER n] Evaluating test|train: L1 .. PSNR .." lines
     --save_iterations      <model_path>/point_cloud/iteration_<n>/point_cloud.ply (before the optimiser step, as there)
     --checkpoint_iterations / --start_checkpoint   <model_path>/chkpnt<n>.pth (checkpoint.py: the reference's tuple)
+    --depth_priors DIR     <image_name>.npy depth (or inverse-depth) priors of the training views: the Pearson depth loss of
+                           depth_prior.py (both --step modes; --depth_prior_mode depth|disparity, --depth_prior_weight, --depth_prior_local with
+                           --depth_prior_patch, --depth_prior_from / --depth_prior_until, --depth_prior_alpha_min)
     --densify adc|mcmc     adc (default): the reference's clone / split / prune; mcmc: mcmc.McmcSchedule -- relocation, growth to
                            --cap_max and position noise (--noise_lr, --opacity_reg, --scale_reg); --step schedule only
 
@@ -87,11 +90,26 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--noise_lr", type=float, default=5e5)
     p.add_argument("--opacity_reg", type=float, default=0.01)
     p.add_argument("--scale_reg", type=float, default=0.01)
+    p.add_argument("--depth_priors", default=None, help="folder of <image_name>.npy priors (float32 / float64 [H,W], any size; "
+                                                        "<image_name>_mask.png optional) for the training views")
+    p.add_argument("--depth_prior_mode", choices=("depth", "disparity"), default="depth",
+                   help='"disparity": the prior is an inverse depth (MiDaS / DepthAnything output)')
+    p.add_argument("--depth_prior_weight", type=float, default=0.0, help="weight of 1 - rho over the whole image")
+    p.add_argument("--depth_prior_local", type=float, default=0.0, help="weight of the mean of 1 - rho over the patches")
+    p.add_argument("--depth_prior_patch", type=int, default=64, help="patch size of the local term, 8 .. 256")
+    p.add_argument("--depth_prior_from", type=int, default=0)
+    p.add_argument("--depth_prior_until", type=int, default=None)
+    p.add_argument("--depth_prior_alpha_min", type=float, default=0.0, help="pixels with rendered alpha below this are not used")
     return p
 
 
 def check_args(args) -> None:
     """The rules between the flags; ValueError with the reason."""
+    wg, wl = getattr(args, "depth_prior_weight", 0.0) or 0.0, getattr(args, "depth_prior_local", 0.0) or 0.0
+    if (wg != 0.0 or wl != 0.0) and not getattr(args, "depth_priors", None):
+        raise ValueError("--depth_prior_weight / --depth_prior_local need --depth_priors DIR, the folder of the priors")
+    if wl != 0.0 and not 8 <= getattr(args, "depth_prior_patch", 64) <= 256:
+        raise ValueError("--depth_prior_local needs --depth_prior_patch in 8 .. 256")
     if getattr(args, "densify", "adc") != "mcmc":
         return
     if getattr(args, "cap_max", None) is None or args.cap_max < 1:
@@ -134,7 +152,7 @@ def run(args) -> dict:
     scene = Scene.from_dataset(args.source_path, model, images=args.images, eval=args.eval, n_views=args.n_views,
                                dataset_name=args.dataset_name, suffix=args.suffix, resolution=args.resolution,
                                white_background=args.white_background, init_points=args.init_points,
-                               model_path=args.model_path, device=dev)
+                               model_path=args.model_path, device=dev, depth_priors=getattr(args, "depth_priors", None))
     model.training_setup(args)
     first_iter = 0
     if args.start_checkpoint:
@@ -157,6 +175,12 @@ def run(args) -> dict:
               densify_until_iter=args.densify_until_iter, densification_interval=args.densification_interval,
               densify_grad_threshold=args.densify_grad_threshold, test_cameras=scene.getTestCameras(),
               test_iterations=args.test_iterations, after_report=after_report)
+    if getattr(args, "depth_priors", None):
+        from .depth_prior import PriorTerm
+        # (its own generator: the view and shift draws below do not move when the term is switched on)
+        kw["depth_prior"] = PriorTerm(mode=args.depth_prior_mode, weight=args.depth_prior_weight, local=args.depth_prior_local,
+                                      patch=args.depth_prior_patch, from_iter=args.depth_prior_from, until_iter=args.depth_prior_until,
+                                      alpha_min=args.depth_prior_alpha_min, seed=args.seed)
     if getattr(args, "step", "schedule") == "graph":
         from .graph_trainer import GraphTrainer
         sched = GraphTrainer(model, scene, PipelineParams(), background, save_iterations=args.save_iterations,

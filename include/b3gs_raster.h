@@ -1650,6 +1650,79 @@ size_t b3gs_mcmc_workspace_bytes(int32_t P);
 int b3gs_mcmc_relocate(const B3gsMcmcIO* io, void* workspace, b3gs_stream_t stream);
 int b3gs_mcmc_views(int32_t P, void* workspace, B3gsMcmcViews* out);
 
+/* ---- depth priors: Pearson depth loss and prior preparation (added to ABI 18; csrc/depthprior.hip,
+ * binocular3dgs_amd/depth_prior.py) --------------------------------------------------------------
+ * Three entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * tests/depth_prior_ref.py restates every rule below in numpy float64.
+ *
+ * 1. b3gs_depth_prior_loss_batch: per view the scale- and shift-invariant loss
+ *      L = w_global (1 - rho_image) + w_local mean over the counted patches of (1 - rho_patch)
+ *    between the rendered depth D and a prior P, and dL/dD.  All arithmetic is fp64, only + - * / sqrt, every statement one
+ *    rounded operation in the order written.  Pixel i (row-major) is USED iff mask_i != 0 and alpha_i >= alpha_min.
+ *      B3GS_DEPTH_PRIOR_DEPTH      x = D,               t' = 1
+ *      B3GS_DEPTH_PRIOR_DISPARITY  x = 1 / (D + 1e-5),  t' = 0 - x x
+ *    with y = P; the six quantities of a pixel are q = (1, x, y, x x, y y, x y), all zero for a pixel that is not used.
+ *    The TREE of 256 values v[0..255]: the xor butterfly per group of 64 (d = 32, 16, .., 1: v[l] = v[l] + v[l ^ d]), then
+ *    (g0 + g1) + (g2 + g3) of the four group results.
+ *      image sums  block b holds pixels 256 b .. 256 b + 255; its partial is the TREE of their q.  The sum is the FOLD of the
+ *                  partials: s[l] = the partials l, l + 64, .. added in that order to +0, then the butterfly of s[0..63].
+ *      patch sums  patches of `patch` x `patch` pixels on the grid with origin (-ox, -oy); (ox, oy) = offset_dev[0..1], each
+ *                  clamped to [0, patch - 1], (0, 0) when offset_dev is NULL.  Patch (i, j), 0 <= i < gx = ceil(W / patch) + 1,
+ *                  0 <= j < gy = ceil(H / patch) + 1, has the local pixels k = 0 .. patch^2 - 1 at x = i patch - ox + k % patch,
+ *                  y = j patch - oy + k / patch (outside the image: not used).  v[t] = q of k = t, t + 256, .. added in that
+ *                  order to +0; the sum is the TREE of v.
+ *      a set       with sums (n, Sx, Sy, Sxx, Syy, Sxy):  cxx = Sxx - (Sx Sx) / n, cyy = Syy - (Sy Sy) / n, cxy = Sxy - (Sx Sy) / n.
+ *                  SKIPPED when n < min_valid, or not cxx > 0, or not cyy > 0: term 0, gradient 0, not counted.  Otherwise
+ *                  den = sqrt(cxx cyy), rho = cxy / den, mx = Sx / n, my = Sy / n, term = 1 - rho, and for a used pixel
+ *                  g = (0 - ((y - my) / den - (rho (x - mx)) / cxx)) t'.
+ *      local mean  the FOLD over the patches in index order j gx + i of (term, counted ? 1 : 0); mean = sum / count, 0 if none.
+ *      gradient    dL_ddepth_i = (float)(w_global g_image + (w_local g_patch) / count), each g 0 where it does not apply.
+ *      parts       [L, 1 - rho_image, local mean, n_used, patches counted, rho_image, a, b], L = w_global term + w_local mean;
+ *                  a = cxy / cyy, b = mx - a my: the least-squares fit D ~ a P + b (x ~ a P + b in disparity mode); an image
+ *                  that is skipped reports rho_image = a = b = 0.
+ *    Two launches for all views of the call (sums with the folds done by the last workgroup of a view to arrive; gradient), no
+ *    host read, no allocation, no floating-point atomic.  `workspace`: b3gs_depth_prior_workspace_bytes(W, H, patch) bytes (0
+ *    for bad sizes), 256-byte aligned, ZERO before its first use; a call leaves it ready for the next one (the arrival counter
+ *    at its head resets itself).  1 <= n_views <= 8, 1 <= W, H and W H <= 2^24, patch 0 (no local term; w_local is then taken
+ *    as 0) or 8 .. 256, min_valid >= 2; anything else is B3GS_ERR_ARG before the first HIP call.
+ * 2. b3gs_resize_depth_batch: a prior of any size -> the training size, float32.  Per output pixel (x, y), in float32:
+ *      sx = fma(x + 0.5, (float)Wsrc / (float)W, -0.5), x0 = floor(sx), fx = sx - x0; the same for y;
+ *      w00 = (1 - fx)(1 - fy), w01 = fx (1 - fy), w10 = (1 - fx) fy, w11 = fx fy  (first index: row);
+ *      taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), clamped into the source;
+ *      v = fma(w11, p11, fma(w10, p10, fma(w01, p01, w00 p00))), a tap of weight 0 entering as 0.
+ *    A source pixel is valid iff it is finite and > 0 (and, with src_mask, its mask byte != 0); an output pixel is valid iff
+ *    every tap of non-zero weight is: then prior = v, mask = 1, else prior = 0, mask = 0.  Equal sizes copy the valid pixels
+ *    bit for bit.  One launch for all views. */
+#define B3GS_DEPTH_PRIOR_DEPTH 0
+#define B3GS_DEPTH_PRIOR_DISPARITY 1
+#define B3GS_DEPTH_PRIOR_MAX_VIEWS 8
+typedef struct B3gsDepthPriorIO {
+  int32_t W, H;
+  const float* depth;          /* [H, W] rendered depth */
+  const float* alpha;          /* [H, W] rendered alpha */
+  const float* prior;          /* [H, W] */
+  const uint8_t* mask;         /* [H, W] validity of the prior */
+  int32_t mode;                /* B3GS_DEPTH_PRIOR_DEPTH / _DISPARITY */
+  int32_t patch;               /* 0, or 8 .. 256 */
+  int32_t min_valid;           /* >= 2 */
+  float alpha_min;
+  double w_global, w_local;
+  const int32_t* offset_dev;   /* NULL, or 2 words on the device: (ox, oy) */
+  float* dL_ddepth;            /* [H, W], every word written */
+  double* parts;               /* [8] on the device */
+  void* workspace;
+} B3gsDepthPriorIO;
+typedef struct B3gsDepthResizeIO {
+  int32_t Wsrc, Hsrc, W, H;
+  const float* src;            /* [Hsrc, Wsrc] */
+  const uint8_t* src_mask;     /* NULL, or [Hsrc, Wsrc] */
+  float* prior;                /* [H, W] */
+  uint8_t* mask;               /* [H, W] */
+} B3gsDepthResizeIO;
+size_t b3gs_depth_prior_workspace_bytes(int32_t W, int32_t H, int32_t patch);
+int b3gs_depth_prior_loss_batch(int32_t n_views, const B3gsDepthPriorIO* io, b3gs_stream_t stream);
+int b3gs_resize_depth_batch(int32_t n_views, const B3gsDepthResizeIO* io, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
