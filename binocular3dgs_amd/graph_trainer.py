@@ -1,13 +1,14 @@
 """The training iteration of schedule.IterationSchedule (train.py:83-198) on the build's own step, ONE HIP-graph replay per
 iteration: FusedRasterizer + ViewShardedStep + binocular_loss_fused + FusedAdam(decay_first=True).
 
-`GraphTrainer` has IterationSchedule's keyword surface and its `run_iteration(it, view_index, shift)`, so train.run builds
+`GraphTrainer` sits on schedule.TrainerBase as IterationSchedule does -- the same keyword surface, the same per-iteration
+plan and report point -- and has its `run_iteration(it, view_index, shift)`, so train.run builds
 either one and the caller's draws (random.choice, torch.rand(1), random.choice) are the ones the schedule mode consumes.
 
 What a captured graph fixes, and where each per-iteration value therefore lives
     the input view / its shifted partner     camera.CameraPairSlots: 71 floats rewritten in place, one pinned upload
     the shift                                CameraPairSlots.trans_dist_dev (B3gsLossIO::trans_dist_dev)
-    the ground-truth image, the mask         copied into static buffers (the mask: gt_alpha_mask, else bg_mask, schedule.py:95-98)
+    the ground-truth image, the mask         copied into static buffers (the mask: schedule.mask_kind -- gt_alpha_mask, else bg_mask)
     the background colour                    three floats of a static block (refreshed when the caller hands in another tensor)
     the depth prior, its validity, the       copied into static buffers next to the mask; the patch offsets: two int32 words
     patch offsets (depth_prior.PriorTerm)    (PriorTerm.offset_buffer) the kernels read, one pinned upload per draw
@@ -20,7 +21,8 @@ What cannot live in device memory is a SHAPE of the graph, captured at its first
 the fifth entry is there while the depth-prior term is active (all training views carry a prior, or none: a mixed set is
 refused) and ABSENT otherwise, so a run without priors has the keys, the events and the launches it always had;
 the decay switches on once (`it > densify_from_iter`), the statistics switch off once (`it >= densify_until_iter`, only with
-the decay off: with it on, densification runs to the end, schedule.py:119-120).  Every kept graph is dropped, and captured
+the decay off: with it on, densification runs to the end).  These windows are schedule.TrainerBase.plan, the one place
+that decides them for both trainers; "the replay carries Adam" is its `step and not densify`.  Every kept graph is dropped, and captured
 again at its next use, exactly when an address or a launch argument changed: after densify_and_prune (P), after
 oneupSHdegree raised the degree, after a capacity check changed `seg1_fraction` / the depth-key width or grew the buffers.
 `captures` counts them.
@@ -55,6 +57,8 @@ import collections
 import gc
 
 import torch
+
+from .schedule import TrainerBase, mask_kind
 
 Draw = collections.namedtuple("Draw", "it view shift bg lr key full offset", defaults=(None,))
 
@@ -129,12 +133,6 @@ class FusedBackend:
         self.focal_x = v0.get_focal()[0]
 
     # ---- what the policy asks ------------------------------------------------------------------------------------------
-    def mask_kind(self, view_index):
-        cam = self.views[view_index]
-        if getattr(cam, "gt_alpha_mask", None) is not None:
-            return "alpha"
-        return "bg" if getattr(cam, "bg_mask", None) is not None else None
-
     def steps(self) -> int:
         return int(self.opt.step_count.item())
 
@@ -251,36 +249,22 @@ class FusedBackend:
                                          noise=noise)
 
 
-class GraphTrainer:
-    """IterationSchedule's surface (model, scene, pipe, background + its keywords) on the graph-replayed fused step.
-    Extra keywords: `save_iterations` / `checkpoint_iterations` (where `after_report` / the caller write files: the capacity
-    word is settled first), `check_every`, `binning_capacity`, `backend` (tests), `events` (a list that receives what ran)."""
+class GraphTrainer(TrainerBase):
+    """IterationSchedule's surface (model, scene, pipe, background + the keywords of schedule.TrainerBase) on the
+    graph-replayed fused step.  Keywords of its own: `save_iterations` / `checkpoint_iterations` (where `after_report` / the
+    caller write files: the capacity word is settled first), `check_every`, `binning_capacity`, `backend` (tests), `events`
+    (a list that receives what ran)."""
 
-    def __init__(self, model, scene, pipe, background, *, ops=None, iterations=30_000, shift_cam_start=20_000,
-                 binocular=True, opacity_decay_factor=0.995, lambda_dssim=0.2, densify_from_iter=500,
-                 densify_until_iter=15_000, densification_interval=100, densify_grad_threshold=0.0002, min_opacity=0.005,
-                 sh_interval=1000, smooth_weight=0.05, log_item=False, before_densify=None, test_cameras=None,
-                 test_iterations=(), report_fn=None, after_report=None, save_iterations=(), checkpoint_iterations=(),
-                 check_every=32, binning_capacity=None, backend=None, events=None, depth_prior=None):
+    def __init__(self, model, scene, pipe, background, *, ops=None, log_item=False, save_iterations=(),
+                 checkpoint_iterations=(), check_every=32, binning_capacity=None, backend=None, events=None, **kw):
         if ops is not None or log_item:
             raise ValueError("GraphTrainer runs the fused step: `ops` and `log_item` belong to IterationSchedule")
-        self.model, self.scene, self.pipe, self.background = model, scene, pipe, background
-        self.iterations, self.shift_cam_start, self.binocular = iterations, shift_cam_start, binocular
-        self.decay = opacity_decay_factor
-        self.densify_from_iter, self.densify_until_iter = densify_from_iter, densify_until_iter
-        self.densification_interval, self.grad_threshold, self.min_opacity = densification_interval, densify_grad_threshold, \
-            min_opacity
-        self.sh_interval, self.before_densify = sh_interval, before_densify
-        self.test_cameras, self.test_iterations = list(test_cameras or []), frozenset(test_iterations)
+        super().__init__(model, scene, pipe, background, **kw)
         self.save_iterations, self.checkpoint_iterations = frozenset(save_iterations), frozenset(checkpoint_iterations)
-        self.report_fn, self.reports, self.after_report = report_fn, {}, after_report
-        self.views = list(scene.getTrainCameras())
         self.check_every = int(check_every)
-        self.backend = backend if backend is not None else FusedBackend(model, self.views, background, lambda_dssim,
-                                                                        smooth_weight, binning_capacity, depth_prior)
-        self.depth_prior = depth_prior
+        self.backend = backend if backend is not None else FusedBackend(model, self.views, background, self.lam,
+                                                                        self.smooth_weight, binning_capacity, self.depth_prior)
         self.events = events
-        self.densified = False
         self.captures = 0        # graphs captured so far: a replay does not move it
         self.grown = 0           # capacity events settled
         self.repeated = 0        # iterations repeated after them
@@ -349,37 +333,28 @@ class GraphTrainer:
             m.oneupSHdegree()
             if m.active_sh_degree != before:
                 self._invalidate("SH degree")
-        pair = bool(self.binocular and it > self.shift_cam_start)
-        decay_on = self.decay is not None and it > self.densify_from_iter
-        if decay_on:
-            self.densify_until_iter = self.iterations       # with the decay on, densification runs to the end
-        stats = it < self.densify_until_iter
-        densify = stats and it > self.densify_from_iter and it % self.densification_interval == 0
-        adam = it < self.iterations and not densify
+        plan = self.plan(it)
+        adam = plan.step and not plan.densify               # the replay carries Adam; the other iterations run eagerly
         # train.py:166-169 -- before this iteration's replay: the parameters are the ones the reference reports and saves
-        if it in self.test_iterations or it in self.save_iterations:
+        if plan.report or it in self.save_iterations:
             self.settle()
-        if it in self.test_iterations:
-            if self.report_fn is None:
-                from .evaluate import training_report
-                self.report_fn = training_report
-            self.reports[it] = self.report_fn(m, self.test_cameras, self.views, self.background)
+        self._report(it, plan)
+        if plan.report:
             self._ev("report", it=it)
         if self.after_report is not None:
-            self.after_report(it)
             self._ev("after_report", it=it)
-        key = (pair, float(self.decay) if (decay_on and adam) else 0.0, bool(stats), b.mask_kind(view_index))
+        key = (plan.pair, float(self.decay) if (plan.decay and adam) else 0.0, plan.stats, mask_kind(self.views[view_index]))
         offset = None
         if getattr(b, "has_prior", False) and self.depth_prior.active(it):
             key, offset = key + ("prior",), self.depth_prior.draw_offset()      # (the term's own generator; kept for a repeat)
-        self._run(Draw(it, view_index, float(shift) if pair else None, self.background, lr, key, adam, offset))
+        self._run(Draw(it, view_index, float(shift) if plan.pair else None, self.background, lr, key, adam, offset))
         self.densified = False
         if not adam:
             self.settle()                                   # before a densification; and no run ends on a raised word
-            if decay_on:
+            if plan.decay:
                 b.decay(self.decay)
                 self._ev("decay", it=it)
-            if densify:
+            if plan.densify:
                 if self.before_densify is not None:
                     self.before_densify(it)
                 noise, m.split_noise = getattr(m, "split_noise", None), None

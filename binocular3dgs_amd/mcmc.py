@@ -131,7 +131,10 @@ class McmcSchedule(IterationSchedule):
     """The iteration of schedule.IterationSchedule with the strategy swapped: the loss gains opacity_reg mean(opacity) +
     scale_reg mean(scaling); no densification statistics; relocate then grow every densification_interval after
     densify_from_iter and before densify_until_iter; inject_noise after optimizer.step() with that iteration's position
-    learning rate.  The opacity decay stays under the caller's switch (opacity_decay_factor=None: off)."""
+    learning rate.  The opacity decay stays under the caller's switch (opacity_decay_factor=None: off) and does not
+    extend the window."""
+    keeps_stats = False
+    decay_extends_densification = False
 
     def __init__(self, model, scene, pipe, background, *, cap_max: int, seed: int = 0, noise_lr: float = 5e5, opacity_reg: float = 0.01,
                  scale_reg: float = 0.01, log_relocations: bool = False, **kw):
@@ -143,57 +146,17 @@ class McmcSchedule(IterationSchedule):
         # log_relocations: keep (src, count, rank, weight_scan, head) of every relocate() as device tensors, by iteration
         self.log_relocations, self.relocation_log = bool(log_relocations), {}
 
-    def run_iteration(self, it: int, view_index: int, shift: float | None = None):
-        m, ops = self.model, self.ops
-        lr_xyz = m.update_learning_rate(it)
-        if it % self.sh_interval == 0:
-            m.oneupSHdegree()
-        cam = self.views[view_index]
-        first = ops.render(cam, m, self.pipe, self.background)
-        target = cam.original_image.to(self.background.device)
-        stereo = 0.0
-        if self.binocular and it > self.shift_cam_start:
-            stereo = self._stereo_term(cam, first, target, float(shift))
-        coverage = 0.0
-        if getattr(cam, "gt_alpha_mask", None) is not None:
-            coverage = (first["rendered_alpha"].abs() * (1 - cam.gt_alpha_mask)).mean()
-        elif getattr(cam, "bg_mask", None) is not None:
-            coverage = (first["rendered_alpha"].abs() * cam.bg_mask).mean()
-        photo = ops.l1_loss(first["render"], target)
-        recon = (1.0 - self.lam) * photo + self.lam * (1.0 - ops.ssim(first["render"], target))
-        reg = self.opacity_reg * m.get_opacity.mean() + self.scale_reg * m.get_scaling.mean()
-        total = recon + stereo + coverage + reg
-        if self.depth_prior is not None:
-            total = self.depth_prior.add(total, it, cam, first)
-        total.backward()
-        self.densified = False
-        with torch.no_grad():
-            if self.log_item:
-                self.ema = 0.4 * recon.item() + 0.6 * self.ema
-            self._after_backward_mcmc(it, lr_xyz)
-        return total
-
-    def _after_backward_mcmc(self, it, lr_xyz):
+    def _add_loss_terms(self, total):
         m = self.model
-        if it in self.test_iterations:
-            if self.report_fn is None:
-                from .evaluate import training_report
-                self.report_fn = training_report
-            self.reports[it] = self.report_fn(m, self.test_cameras, self.views, self.background)
-        if self.after_report is not None:
-            self.after_report(it)
-        if self.decay is not None and it > self.densify_from_iter:
-            m.opacity_decay(factor=self.decay)
-        if self.densify_from_iter < it < self.densify_until_iter and it % self.densification_interval == 0:
-            if self.before_densify is not None:
-                self.before_densify(it)
-            P = m.get_xyz.shape[0]
-            out = relocate(m, m.optimizer, iteration=it, seed=self.seed, min_opacity=self.min_opacity, debug=self.log_relocations)
-            if self.log_relocations:
-                self.relocation_log[it] = out
-            self.densified = grow(m, m.optimizer, self.cap_max, iteration=it, seed=self.seed, min_opacity=self.min_opacity) != P
-        if it < self.iterations:
-            opt = m.optimizer
-            opt.step()
-            opt.zero_grad(set_to_none=True)
-            inject_noise(m, lr_xyz, iteration=it, seed=self.seed, noise_lr=self.noise_lr)
+        return total + (self.opacity_reg * m.get_opacity.mean() + self.scale_reg * m.get_scaling.mean())
+
+    def _densify(self, it):
+        m = self.model
+        P = m.get_xyz.shape[0]
+        out = relocate(m, m.optimizer, iteration=it, seed=self.seed, min_opacity=self.min_opacity, debug=self.log_relocations)
+        if self.log_relocations:
+            self.relocation_log[it] = out
+        self.densified = grow(m, m.optimizer, self.cap_max, iteration=it, seed=self.seed, min_opacity=self.min_opacity) != P
+
+    def _after_step(self, it, lr_xyz):
+        inject_noise(self.model, lr_xyz, iteration=it, seed=self.seed, noise_lr=self.noise_lr)

@@ -205,12 +205,11 @@ def run(args) -> dict:
         if it in args.checkpoint_iterations:
             say("\n[ITER {}] Saving Checkpoint".format(it))
             checkpoint.save(args.model_path + "/chkpnt" + str(it) + ".pth", model, model.optimizer, it)
-    if hasattr(sched, "settle"):
-        sched.settle()
+    sched.settle()
     say("\nTraining complete.")
     return {"model_path": args.model_path, "first_iteration": first_iter + 1, "iterations": args.iterations,
             "loss": None if loss is None else float(loss.detach()), "points": int(model.get_xyz.shape[0]), "reports": dict(sched.reports),
-            "scene": scene, "model": model, "captures": getattr(sched, "captures", 0), "trainer": sched}
+            "scene": scene, "model": model, "captures": sched.captures, "trainer": sched}
 
 
 def main(argv=None) -> int:

@@ -72,11 +72,12 @@ class _Model:
         self.replaced = True
 
 
-def _schedule_run(draws, mask=False):
-    """IterationSchedule over recording stand-ins -> {it: [what happened, in order]}"""
+def _schedule_run(draws, mask=False, cls=IterationSchedule, model_cls=_Model, seen=None, **extra):
+    """IterationSchedule (or `cls`, a subclass, with its `extra` keywords) over recording stand-ins -> {it: [what happened,
+    in order]}; `seen(it, sched, total)` is called after every iteration."""
     log = []
     cams = [_Cam(k, torch.ones(1, H, W) if mask else None) for k in range(3)]
-    model = _Model(log)
+    model = model_cls(log)
 
     def render(cam, m, pipe, bg):
         log.append("render:shifted" if isinstance(cam.uid, tuple) else f"render:{cam.uid}")
@@ -91,13 +92,15 @@ def _schedule_run(draws, mask=False):
     ops = types.SimpleNamespace(render=render, l1_loss=lambda a, b, mask=None: (a - b).abs().mean(),
                                 ssim=lambda a, b: (a * b).mean(), SmoothLoss=Smooth,
                                 inverse_warp_images=lambda img, disp, r, c: img * 1.0 + disp.mean() * 0.0)
-    sched = IterationSchedule(model, _Scene(cams), None, torch.zeros(3), ops=ops, test_cameras=[], test_iterations=TEST_ITERS,
-                              report_fn=lambda *a: log.append("report") or {}, after_report=lambda it: log.append(
-                                  "save" if it in SAVE_ITERS else "after_report"), **CFG)
+    sched = cls(model, _Scene(cams), None, torch.zeros(3), ops=ops, test_cameras=[], test_iterations=TEST_ITERS,
+                report_fn=lambda *a: log.append("report") or {}, after_report=lambda it: log.append(
+                    "save" if it in SAVE_ITERS else "after_report"), **CFG, **extra)
     out = {}
     for it, view, shift in draws:
         del log[:]
-        sched.run_iteration(it, view, shift)
+        total = sched.run_iteration(it, view, shift)
+        if seen is not None:
+            seen(it, sched, total)
         if it in CKPT_ITERS:
             log.append("checkpoint")
         out[it] = list(log)
@@ -225,7 +228,7 @@ def test_every_iteration_does_what_the_schedule_does(mask):
         w = want[it]                                       # the schedule itself: report / save sit before decay, as recorded
         if "report" in w and "decay" in w:
             assert w.index("report") < w.index("decay")
-    # the windows of schedule.py:119-135 were really crossed
+    # the windows of schedule.TrainerBase.plan were really crossed
     flat = [e for it in got for e in got[it]]
     assert flat.count("densify") == 4 and flat.count("report") == 2 and flat.count("save") == 2
     assert "adam" not in got[CFG["iterations"]] and "adam" not in got[10] and "decay" not in got[8] and "decay" in got[9]
@@ -287,3 +290,83 @@ def test_an_overflow_word_repeats_exactly_the_dropped_draws():
     # a word raised in the last iteration is settled before the run ends
     tr2, b2, ev2, _ = _graph_run(draws, raise_at=48)
     assert [e["repeat"] for e in ev2 if e["event"] == "overflow"] == [[48]] and b2.word == 0
+
+
+class _McmcModel(_Model):
+    """_Model with what McmcSchedule reads besides: P rows, their opacities and scales"""
+
+    def __init__(self, log):
+        super().__init__(log)
+        self.get_xyz = torch.zeros(5, 3)
+        self.get_opacity = torch.linspace(0.05, 0.9, 5)[:, None]
+        self.get_scaling = torch.linspace(0.01, 0.7, 15).reshape(5, 3)
+
+
+def test_mcmc_schedule_swaps_the_strategy_and_nothing_else(monkeypatch):
+    """McmcSchedule over the stand-ins of IterationSchedule's run above, its three device calls replaced by recorders: per
+    iteration the same renders, report and save points and decay as the schedule; relocate + grow inside
+    (densify_from_iter, densify_until_iter) only -- the decay does not extend that window; no statistics; the noise right
+    after every optimiser step with that iteration's position learning rate; the total is the schedule's plus the
+    regulariser, added last."""
+    from binocular3dgs_amd import mcmc
+    draws = _draws()
+    P, cap, seed, o_reg, s_reg = 5, 64, 9, 0.02, 0.03
+    grown = {10: 6, 20: 5}                 # what grow() answers: P moved at 10, not at 20
+    base, plain_totals, totals, densified, noise = {}, {}, {}, {}, {}
+
+    def relocate(model, optimizer, *, iteration, seed, min_opacity, debug):
+        model.log.append("relocate")
+        return ("relocated", iteration) if debug else None
+
+    def grow(model, optimizer, cap_max, *, iteration, seed, min_opacity):
+        assert cap_max == cap
+        model.log.append("grow")
+        return grown[iteration]
+
+    def inject_noise(model, lr_xyz, *, iteration, seed, noise_lr):
+        model.log.append("noise")
+        noise[iteration] = (lr_xyz, iteration, seed, noise_lr)
+
+    monkeypatch.setattr(mcmc, "relocate", relocate)
+    monkeypatch.setattr(mcmc, "grow", grow)
+    monkeypatch.setattr(mcmc, "inject_noise", inject_noise)
+
+    want = _schedule_run(draws, mask=True, seen=lambda it, s, total: plain_totals.__setitem__(it, total.detach()))
+
+    def seen(it, sched, total):
+        totals[it], densified[it] = total.detach(), sched.densified
+        base.setdefault("sched", sched)
+    got = _schedule_run(draws, mask=True, cls=mcmc.McmcSchedule, model_cls=_McmcModel, seen=seen, cap_max=cap, seed=seed,
+                        noise_lr=123.0, opacity_reg=o_reg, scale_reg=s_reg, log_relocations=True)
+    sched = base["sched"]
+    last = CFG["iterations"]
+    for it, _, _ in draws:
+        g, w = got[it], want[it]
+        assert ("relocate" in g, "grow" in g) == ((it in (10, 20)),) * 2, (it, g)
+        if it in (10, 20):
+            assert g.index("relocate") + 1 == g.index("grow")
+        assert "densify" not in g and ("densify" in w) == (it in (10, 20, 30, 40)), (it, g, w)
+        assert "stats" not in g, (it, g)
+        assert ("decay" in g) == (it >= 9), (it, g)
+        if it < last:
+            assert g.count("adam") == 1 and g.count("noise") == 1 and g.index("adam") + 1 == g.index("noise"), (it, g)
+            assert noise[it] == (1e-4 / it, it, seed, 123.0)
+        else:
+            assert "adam" not in g and "noise" not in g and it not in noise
+        assert ("report" in g) == (it in TEST_ITERS) and ("save" in g) == (it in SAVE_ITERS), (it, g)
+        for point in ("report", "save"):
+            if point in g and "decay" in g:
+                assert g.index(point) < g.index("decay"), (it, g)
+        assert ("render:shifted" in g) == (it >= 15), (it, g)
+        # everything the strategy does not own is the schedule's, in the schedule's order (the optimiser step: above)
+        own = ("relocate", "grow", "noise", "densify", "stats", "adam")
+        assert [e for e in g if e not in own] == [e for e in w if e not in own], (it, g, w)
+        m = sched.model
+        reg = o_reg * m.get_opacity.mean() + s_reg * m.get_scaling.mean()
+        assert float(totals[it]) == float(plain_totals[it] + reg), (it, float(totals[it]), float(plain_totals[it] + reg))
+        assert densified[it] == (it in grown and grown[it] != P), it
+    # (on a densification iteration the schedule's optimiser step finds no gradient; MCMC's does step)
+    for it in (10, 20):
+        assert "adam" in got[it] and "adam" not in want[it]
+    assert sorted(sched.relocation_log) == [10, 20] and sched.relocation_log[10] == ("relocated", 10)
+    assert sched.seed == seed and sched.densify_until_iter == CFG["densify_until_iter"]
