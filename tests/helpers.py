@@ -580,3 +580,232 @@ def binning_views(d, sizes, shifts=None):
 #   "span": "min key KEY27_BASE + 1, max key KEY27_BASE + 2^27 - 3, both in the lists", "span_out": "max key KEY27_BASE + 2^27 - 2",
 #   "count<N>": "N instances, five Gaussians of two tiles", "cover": "two Gaussians of 100 tiles at depth ranks 255 and 256",
 #   "sparse": "V <= 0.25 P", "onetile": "one distinct tile id, N > 8192", "tiles<T>": "exactly T distinct tile ids",
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Scenes of the projection edge tests (tests/test_projection_ref_cpu.py, tests/test_gpu_projection_edges.py; reference:
+# tests/projection_ref.py): edge_scene with the branches of the forward projection populated on purpose.  WHICH stratum a
+# Gaussian belongs to in a view is decided by the float64 reference (projection_strata), never by construction alone.
+# ---------------------------------------------------------------------------------------------------------------------
+PROJ_P = 829                          # no multiple of 64 or 256; three 256-thread blocks and a tail
+PROJ_SIZES = ((80, 48), (75, 33), (33, 17))
+PROJ_SH_CONFIGS = ((1, 0), (4, 0), (4, 1), (9, 2), (16, 1), (16, 3))          # (stored K, active degree)
+PROJ_NEAR_Z = tuple(float(v) for v in (np.float32(0.2), np.nextafter(np.float32(0.2), np.float32(0)), np.nextafter(np.float32(0.2), np.float32(1)),
+                                       np.float32(0.2) * np.float32(1 - 1e-3), np.float32(0.2) * np.float32(1 + 1e-3)))
+PROJ_CAM_B_TZ = 2.0 ** -6             # camera B: identity rotation, this translation along z: view z = z_world + 2^-6 exactly
+PROJ_FAINT_BANDS = ((0.0030, 0.0039), (0.0039, 1.0 / 255), (1.0 / 255, 0.0040), (0.0040, 0.006))
+PROJ_STRATA = ("clamp_x", "clamp_y", "clamp_xy", "edge_l", "edge_r", "edge_t", "edge_b", "align", "faint", "solid", "needle", "speck",
+               "sheet", "ch1", "ch2", "ch3", "quat")
+PROJ_FLOORS = dict(align=10)          # non-fragile members; every other stratum: 20 (near: 6 per value, faint: 8 per band)
+# Bounds of the float record words against the float64 reference: 10 x the largest 99th percentile of oracle/tile_ref.c
+# (float32) against tests/projection_ref.py over every scene, camera, size and SH configuration above
+# (tests/test_projection_ref_cpu.py measures and pins them; the table is in tests/test_gpu_projection_edges.py).
+# |err| / (1 + |x|); the conic against the largest conic entry of its Gaussian.
+PROJ_POS_BOUND, PROJ_CONIC_BOUND, PROJ_RGB_BOUND, PROJ_DEPTH_BOUND = 1.5e-5, 4.1e-5, 1.2e-6, 8.4e-7
+
+
+def projection_cameras(W, H):
+    """{"A": the yaw-8 camera of synth_view_set, "A2": its binocular partner, "B": the axis-aligned near-plane camera}"""
+    cam, partner, _t = synth.synth_view_set(W, H)[1]
+    fovx = math.radians(60.0)
+    b = Camera(np.eye(3), np.array([0.0, 0.0, PROJ_CAM_B_TZ]), fovx, synth.fovy_from(fovx, W, H), W, H)
+    return {"A": cam, "A2": partner, "B": b}
+
+
+def with_camera(d, cam):
+    """scene dict d seen by another camera (its own size and field of view)"""
+    v = dict(d)
+    v.update(viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, campos=cam.camera_center,
+             W=cam.image_width, H=cam.image_height, tanfovx=math.tan(cam.FoVx / 2), tanfovy=math.tan(cam.FoVy / 2))
+    return v
+
+
+def projection_scene(W=80, H=48, K=16, sh_degree=3, seed=0):
+    """edge_scene(P = 829, scale_modifier 0.8, stratum A placed for camera A and its partner in turn) with further Gaussians
+    planted among its last half, then all rows permuted (i -> 367 i mod 829) so that every wave holds several kinds.
+    -> (d, cams, planted): d as edge_scene's (camera A; with_camera for the others), cams = projection_cameras,
+    planted = {name: indices} of what was placed where (the strata are decided by projection_strata).  Placed in pixel units
+    of camera A at size W x H; near: on camera B's axis at the five view depths PROJ_NEAR_Z."""
+    cams = projection_cameras(W, H)
+    d, _cam, _built = edge_scene(P=PROJ_P, W=W, H=H, seed=seed, K=K, sh_degree=sh_degree, place_cams=[cams["A"], cams["A2"]])
+    d = with_camera(d, cams["A"])
+    P, nA = PROJ_P, PROJ_P // 4
+    rng = np.random.RandomState(1000 * seed + W)
+    tx, ty = d["tanfovx"], d["tanfovy"]
+    fx = W / (2 * tx)
+    means, scales, opac = d["means3D"].double().numpy().copy(), d["scales"].double().numpy().copy(), d["opacities"].double().numpy().reshape(-1).copy()
+    rot, shs = d["rotations"].double().numpy().copy(), d["shs"].double().numpy().copy()
+    Va = cams["A"].world_view_transform.double().numpy()
+    to_world = lambda pv: (pv - Va[3, :3]) @ np.linalg.inv(Va[:3, :3])  # noqa: E731
+    pix = lambda px, py, z: np.stack([z * tx * ((2 * px + 1) / W - 1), z * ty * ((2 * py + 1) / H - 1), z], 1)  # noqa: E731
+    sigma = lambda s_px, z: s_px * z / (fx * 0.8)  # noqa: E731      (world scale of a splat of s_px pixels at depth z)
+    nxt = [2 * nA]
+    planted = {}
+
+    def take(name, n):
+        idx = np.arange(nxt[0], nxt[0] + n)
+        nxt[0] += n
+        assert nxt[0] <= P
+        planted[name] = idx
+        return idx
+
+    # three channels lowered for good in a part of stratum B (edge_scene lowers them by chance)
+    b3 = nA + np.arange(3, nA, 4)[:40]
+    shs[b3, 0] -= 1.2 / SH_C0
+    # near the clamp limit: |x/z| (|y/z|) within 2 % of 1.3 tan
+    i = take("clamp_near", 32)
+    z = rng.uniform(2, 6, 32)
+    f = 1.3 * (1 + rng.uniform(-0.02, 0.02, (32, 2))) * rng.choice([-1.0, 1.0], (32, 2))
+    inner = rng.uniform(-0.9, 0.9, (32, 2))
+    kind = np.arange(32) % 3
+    means[i] = to_world(np.stack([np.where(kind != 1, f[:, 0], inner[:, 0]) * tx * z, np.where(kind != 0, f[:, 1], inner[:, 1]) * ty * z, z], 1))
+    scales[i] = (0.25 * z * np.exp(0.3 * rng.normal(size=32)))[:, None] * np.ones(3)
+    opac[i] = rng.uniform(0.03, 0.15, 32)
+    # centre outside the image on one side; every second one wide enough to reach in
+    for name in ("edge_l", "edge_r", "edge_t", "edge_b"):
+        n = 28
+        i = take(name, n)
+        z = rng.uniform(2, 6, n)
+        span, other = (W, H) if name[-1] in "lr" else (H, W)
+        dist = rng.uniform(1.0, max(2.0, 0.12 * span), n)            # (beyond 0.15 of the image the Jacobian clamp sets in)
+        reach = np.arange(n) % 2 == 0
+        beyond = 16 * ((span + 15) // 16) - span if name[-1] in "rb" else 0      # the partial last tile still belongs to the grid
+        s_px = np.where(reach, (dist + rng.uniform(2, 12, n)) / 3.0, 0.05)
+        dist = np.where(reach, dist, dist + beyond + 3.5)
+        along = rng.uniform(0, other - 1, n)
+        c = -0.5 - dist if name[-1] in "lt" else span - 0.5 + dist
+        means[i] = to_world(pix(c, along, z) if name[-1] in "lr" else pix(along, c, z))
+        scales[i] = sigma(s_px, z)[:, None] * np.ones(3)
+        opac[i] = rng.uniform(0.2, 0.8, n)
+    # faint: four bands of the activated opacity around the 0.0039 gate and 1/255
+    i = take("faint", 40)
+    band = np.arange(40) % 4
+    lo, hi = np.array(PROJ_FAINT_BANDS)[band].T
+    opac[i] = lo + (hi - lo) * rng.uniform(0.15, 0.85, 40)
+    z = rng.uniform(2, 6, 40)
+    means[i] = to_world(pix(rng.uniform(4, W - 5, 40), rng.uniform(4, H - 5, 40), z))
+    scales[i] = sigma(rng.uniform(2, 9, 40), z)[:, None] * np.exp(0.3 * rng.normal(size=(40, 3)))
+    i = take("solid", 24)
+    opac[i] = rng.uniform(0.99, 0.9999, 24)
+    z = rng.uniform(2, 6, 24)
+    means[i] = to_world(pix(rng.uniform(0, W - 1, 24), rng.uniform(0, H - 1, 24), z))
+    scales[i] = sigma(rng.uniform(1, 6, 24), z)[:, None] * np.exp(0.3 * rng.normal(size=(24, 3)))
+    i = take("needle", 26)
+    z = rng.uniform(2, 6, 26)
+    means[i] = to_world(pix(rng.uniform(0, W - 1, 26), rng.uniform(0, H - 1, 26), z))
+    long_ = sigma(rng.uniform(4, 12, 26), z)     # (longer: the float32 determinant cancels, errors of the ORACLE past 10 x its 99th percentile)
+    scales[i] = long_[:, None] / rng.uniform(300, 1000, (26, 3))
+    scales[i, rng.randint(0, 3, 26)] = long_
+    opac[i] = rng.uniform(0.2, 0.8, 26)
+    i = take("speck", 24)
+    z = rng.uniform(2, 6, 24)
+    means[i] = to_world(pix(rng.uniform(0, W - 1, 24), rng.uniform(0, H - 1, 24), z))
+    scales[i] = 1e-4 * z[:, None] * np.ones(3)
+    opac[i] = rng.uniform(0.2, 0.8, 24)
+    i = take("sheet", 22)
+    z = rng.uniform(3, 6, 22)
+    means[i] = to_world(pix(rng.uniform(0.3 * W, 0.7 * W, 22), rng.uniform(0.3 * H, 0.7 * H, 22), z))
+    scales[i] = sigma(rng.uniform(2.0, 4.0, 22) * max(W, H), z)[:, None] * np.ones(3)
+    opac[i] = rng.uniform(0.01, 0.05, 22)
+    # quaternions whose length lies either side of F.normalize's eps = 1e-12; four all-zero rows
+    i = take("quat", 28)
+    v = rng.normal(size=(28, 4))
+    rot[i] = v / np.linalg.norm(v, axis=1, keepdims=True) * np.exp(rng.uniform(math.log(1e-13), math.log(1e-11), 28))[:, None]
+    rot[i[:4]] = 0.0
+    z = rng.uniform(2, 6, 28)
+    means[i] = to_world(pix(rng.uniform(0, W - 1, 28), rng.uniform(0, H - 1, 28), z))
+    scales[i] = sigma(rng.uniform(1, 6, 28), z)[:, None] * np.exp(0.5 * rng.normal(size=(28, 3)))
+    # near plane, camera B (view = world + (0, 0, 2^-6)): the world z is a float32 and the sum is exact
+    i = take("near", 40)
+    zv = np.array(PROJ_NEAR_Z)[np.arange(40) % 5]
+    zw = (zv - PROJ_CAM_B_TZ).astype(np.float32).astype(np.float64)
+    assert ((zw + PROJ_CAM_B_TZ).astype(np.float32).astype(np.float64) == zv).all() and (zw + PROJ_CAM_B_TZ == zv).all()
+    means[i] = np.stack([zv * tx * rng.uniform(-0.8, 0.8, 40), zv * ty * rng.uniform(-0.8, 0.8, 40), zw], 1)
+    scales[i] = 0.02 * zv[:, None] * np.ones(3)
+    opac[i] = rng.uniform(0.2, 0.8, 40)
+
+    perm = (367 * np.arange(P)) % P                       # row j of the scene = row perm[j] of the construction
+    inv = np.argsort(perm)
+    planted = {k: np.sort(inv[v]) for k, v in planted.items()}
+    t32 = lambda a: torch.tensor(np.asarray(a)[perm], dtype=torch.float32)  # noqa: E731
+    d.update(means3D=t32(means), scales=t32(scales), opacities=t32(opac).reshape(P, 1), rotations=t32(rot), shs=t32(shs))
+    return d, cams, planted
+
+
+def raw_parameters(d):
+    """The raw (pre-activation) parameters a scene dict's activated ones come from: log scales, the quaternion as it is,
+    logit opacity, SH rows split into dc / rest -- float32, what the RAW entry points of the library take."""
+    op = d["opacities"].double().reshape(-1, 1)
+    return dict(xyz=d["means3D"].float().contiguous(), features_dc=d["shs"][:, :1].float().contiguous(),
+                features_rest=d["shs"][:, 1:].float().contiguous(), scaling=torch.log(d["scales"].double()).float(),
+                rotation=d["rotations"].float().contiguous(), opacity=torch.log(op / (1 - op)).float())
+
+
+def torch_activations(d):
+    """d with scales / rotations / opacities replaced by what the reference's accessors make of raw_parameters(d): exp,
+    F.normalize (eps 1e-12), sigmoid in float32 (tests/test_gpu_round5.py pins the kernels' activations to these bits)."""
+    raw = raw_parameters(d)
+    out = dict(d)
+    out.update(scales=torch.exp(raw["scaling"]), rotations=torch.nn.functional.normalize(raw["rotation"]),
+               opacities=torch.sigmoid(raw["opacity"]))
+    return out
+
+
+def projection_strata(o, planted, W, H):
+    """Boolean masks of PROJ_STRATA for one view from the float64 reference's output `o` (projection_ref.project on the
+    activated parameters) -- geometry strata need a visible Gaussian; `planted` only tells needle / speck / sheet / quat /
+    solid / faint candidates apart from the crowd, the property itself is checked on the reference's quantities."""
+    P = len(o["mx"])
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    vis = o["visible"]
+    cand = lambda k: np.isin(np.arange(P), planted[k])  # noqa: E731
+    m = dict(clamp_x=vis & o["clamp_x"] & ~o["clamp_y"], clamp_y=vis & o["clamp_y"] & ~o["clamp_x"], clamp_xy=vis & o["clamp_x"] & o["clamp_y"])
+    zok = o["visible_z"]
+    m["edge_l"], m["edge_r"] = zok & (o["mx"] < -0.5), zok & (o["mx"] > W - 0.5)
+    m["edge_t"], m["edge_b"] = zok & (o["my"] < -0.5), zok & (o["my"] > H - 0.5)
+    rad = o["rad_f"]
+    frac = lambda v: np.abs(v - np.round(v))  # noqa: E731
+    inside = lambda v, hi: (v > 0.5) & (v < hi + 0.5)  # noqa: E731      (an edge value the clamp does not decide)
+    lo, hi_ = (o["mx"] - rad) / 16, (o["mx"] + rad + 15) / 16
+    m["align"] = vis & (((frac(lo) < 0.05) & inside(lo, gx)) | ((frac(hi_) < 0.05) & inside(hi_, gx)))
+    op = o["opacity"]
+    m["faint"] = zok & cand("faint") & (op >= 0.0030) & (op <= 0.006)
+    for b, (lo_, hi2) in enumerate(PROJ_FAINT_BANDS):
+        m[f"faint{b}"] = m["faint"] & (op >= lo_) & (op < hi2 if b < 3 else op <= hi2) & ((op > lo_) if b == 2 else True)
+    m["solid"] = vis & (op >= 0.99)
+    m["needle"] = vis & cand("needle")
+    m["speck"] = vis & cand("speck") & (np.abs(o["a"] - 0.3) < 1e-3) & (np.abs(o["c"] - 0.3) < 1e-3)
+    m["sheet"] = vis & ((o["rect"] == np.array([0, 0, gx, gy])).all(1)) & cand("sheet")
+    n = (o["colour_raw"] < 0).sum(1)
+    m["ch1"], m["ch2"], m["ch3"] = vis & (n == 1), vis & (n == 2), vis & (n == 3)
+    m["quat"] = vis & cand("quat")
+    return m
+
+
+def projection_populations(o, strata, planted, cam, pr):
+    """Assert the floors of one view from the float64 reference (non-fragile members: 20 per stratum, 10 for align, 8 per faint
+    band, 6 per near value with camera B, 8 per kind of every edge stratum) and the 10 % cap on what a stratum loses to
+    fragility -> {stratum: (members, fragile)}"""
+    frag = pr.any_fragile(o)
+    pop = {}
+    for k in PROJ_STRATA + tuple(f"faint{b}" for b in range(4)):
+        n, lost = int(strata[k].sum()), int((strata[k] & frag).sum())
+        pop[k] = (n, lost)
+        floor = 8 if k.startswith("faint") and k != "faint" else PROJ_FLOORS.get(k, 20)
+        assert lost <= 0.1 * n, f"camera {cam}: stratum {k} loses {lost} of {n} members to fragility"
+        assert n - lost >= floor, f"camera {cam}: stratum {k} holds {n} members, {lost} fragile (floor {floor})"
+    for k in ("edge_l", "edge_r", "edge_t", "edge_b"):
+        reach, miss = int((strata[k] & o["visible"] & ~frag).sum()), int((strata[k] & ~o["visible"] & ~frag).sum())
+        pop[k + " reach/miss"] = (reach, miss)
+        assert reach >= 8 and miss >= 8, f"camera {cam}: {k} holds {reach} that reach in and {miss} that do not"
+    if cam == "B":
+        z = o["pv"][planted["near"], 2]
+        counts = [int((z == v).sum()) for v in PROJ_NEAR_Z]
+        pop["near"] = counts
+        assert min(counts) >= 6 and (o["s_near"][planted["near"]] == 0).all(), f"near values {counts}; view z exact"
+        assert (o["visible_z"][planted["near"]] == (z > PROJ_NEAR_Z[0])).all()
+    sp = strata["speck"]
+    assert (o["radius"][sp] == 3).all(), "a speck is the low-pass filter alone: radius ceil(3 sqrt(0.3 + sqrt(0.1))) = 3"
+    ratio = np.sqrt(np.maximum(o["a"], o["c"]) / 0.3)
+    assert (strata["needle"].sum() == 0) or np.median(ratio[strata["needle"]]) > 5
+    return pop

@@ -51,13 +51,15 @@ CAPACITY = 200000
 class _View:
     """One view's device buffers and B3gsScene."""
 
-    def __init__(self, L, d, P):
+    def __init__(self, L, d, P, K=1):
         from binocular3dgs_amd import _lib
         dev = "cuda"
         self.W, self.H, self.P = d["W"], d["H"], P
         self.keep = [d[k].float().contiguous().to(dev) for k in ("bg", "viewmatrix", "projmatrix", "campos")]
         bg, vm, pm, cp = self.keep
-        self.scene = _lib.B3gsScene(P, 0, 1, self.W, self.H, d["tanfovx"], d["tanfovy"], 1.0, 0, 0, bg.data_ptr(), None, None,
+        # (K SH rows stored, the scene's active degree and scale modifier: 1, 0 and 1.0 in the blend and binning scenes)
+        self.scene = _lib.B3gsScene(P, d.get("sh_degree", 0) if K > 1 else 0, K, self.W, self.H, d["tanfovx"], d["tanfovy"],
+                                    d.get("scale_modifier", 1.0), 0, 0, bg.data_ptr(), None, None,
                                     None, None, None, None, None, vm.data_ptr(), pm.data_ptr(), cp.data_ptr())
         u8 = dict(dtype=torch.uint8, device=dev)
         self.geom = torch.zeros(L.b3gs_geometry_bytes(P), **u8)
@@ -104,23 +106,26 @@ class _View:
 class Device:
     """The Gaussians of a scene dict on the device, and the three calls of the blend on views of them."""
 
-    def __init__(self, d):
+    def __init__(self, d, K=1):
+        """K: the SH rows of d["shs"] to store (row 0 in features_dc, rows 1.. in features_rest)"""
         from binocular3dgs_amd import _lib
         self.lib = _lib
         self.L = _lib.lib()
         dev = "cuda"
-        self.P = d["means3D"].shape[0]
+        self.P, self.K = d["means3D"].shape[0], K
         op = d["opacities"].double().reshape(-1, 1)
         self.params = [d["means3D"].float(), d["shs"][:, :1].float(), torch.log(d["scales"].double()).float(),
                        d["rotations"].float(), torch.log(op / (1 - op)).float()]
         self.params = [p.contiguous().to(dev) for p in self.params]
+        self.rest = d["shs"][:, 1:K].float().contiguous().to(dev) if K > 1 else None
         self.rp = _lib.B3gsRawParams()
-        self.rp.xyz, self.rp.features_dc, self.rp.features_rest = self.params[0].data_ptr(), self.params[1].data_ptr(), None
+        self.rp.xyz, self.rp.features_dc = self.params[0].data_ptr(), self.params[1].data_ptr()
+        self.rp.features_rest = None if self.rest is None else self.rest.data_ptr()
         self.rp.scaling, self.rp.rotation, self.rp.opacity = (p.data_ptr() for p in self.params[2:])
         self.stream = torch.cuda.current_stream().cuda_stream
 
     def views(self, ds):
-        return [_View(self.L, d, self.P) for d in ds]
+        return [_View(self.L, d, self.P, self.K) for d in ds]
 
     def _fwd_table(self, views, reference_binning, seg1_fraction=0.0):
         arr = (self.lib.B3gsForwardView * len(views))()
