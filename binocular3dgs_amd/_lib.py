@@ -213,6 +213,16 @@ class B3gsDepthResizeIO(C.Structure):
                 ("src_mask", C.c_void_p), ("prior", C.c_void_p), ("mask", C.c_void_p)]
 
 
+class B3gsExposurePlane(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("in_", C.c_void_p), ("g_out", C.c_void_p), ("out", C.c_void_p), ("A", C.c_void_p),
+                ("row_dev", C.c_void_p), ("V", C.c_int32), ("G", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+class B3gsExposureFitIO(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("render", C.c_void_p), ("gt", C.c_void_p), ("mask", C.c_void_p), ("A", C.c_void_p),
+                ("sums", C.c_void_p), ("flag", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -287,7 +297,9 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: fixed-budget training (MCMC relocation and position noise)
            "b3gs_mcmc_random", "b3gs_mcmc_noise", "b3gs_mcmc_workspace_bytes", "b3gs_mcmc_relocate", "b3gs_mcmc_views",
            # added to ABI 18: depth priors (Pearson depth loss, prior resize)
-           "b3gs_depth_prior_workspace_bytes", "b3gs_depth_prior_loss_batch", "b3gs_resize_depth_batch")
+           "b3gs_depth_prior_workspace_bytes", "b3gs_depth_prior_loss_batch", "b3gs_resize_depth_batch",
+           # added to ABI 18: per-image exposure compensation (apply, backward, fit, row-sparse Adam)
+           "b3gs_exposure_workspace_bytes", "b3gs_exposure_apply", "b3gs_exposure_backward", "b3gs_exposure_fit", "b3gs_exposure_adam")
 
 _lib = None
 
@@ -563,6 +575,16 @@ def lib():
     L.b3gs_depth_prior_loss_batch.restype = C.c_int
     L.b3gs_resize_depth_batch.argtypes = [I32, C.POINTER(B3gsDepthResizeIO), V]
     L.b3gs_resize_depth_batch.restype = C.c_int
+    L.b3gs_exposure_workspace_bytes.argtypes = [I32, I32]
+    L.b3gs_exposure_workspace_bytes.restype = C.c_size_t
+    L.b3gs_exposure_apply.argtypes = [I32, C.POINTER(B3gsExposurePlane), V]
+    L.b3gs_exposure_apply.restype = C.c_int
+    L.b3gs_exposure_backward.argtypes = [I32, C.POINTER(B3gsExposurePlane), V]
+    L.b3gs_exposure_backward.restype = C.c_int
+    L.b3gs_exposure_fit.argtypes = [I32, C.POINTER(B3gsExposureFitIO), V]
+    L.b3gs_exposure_fit.restype = C.c_int
+    L.b3gs_exposure_adam.argtypes = [I32, V, V, V, V, V, V, V, V, C.c_double, C.c_double, C.c_double, V, V]
+    L.b3gs_exposure_adam.restype = C.c_int
     L.b3gs_pose_gradient_workspace_bytes.argtypes = [I32, I32]
     L.b3gs_pose_gradient_workspace_bytes.restype = C.c_size_t
     L.b3gs_pose_gradient.argtypes = [I32, I32, I32, V, V, V, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

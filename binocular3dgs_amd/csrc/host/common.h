@@ -94,5 +94,6 @@ void bind_lod(pybind11::module_& m);
 void bind_poisson(pybind11::module_& m);
 void bind_mcmc(pybind11::module_& m);
 void bind_depthprior(pybind11::module_& m);
+void bind_exposure(pybind11::module_& m);
 
 }  // namespace b3

@@ -72,4 +72,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_poisson(m);
   b3::bind_mcmc(m);
   b3::bind_depthprior(m);
+  b3::bind_exposure(m);
 }

@@ -141,14 +141,30 @@ def _psnr(mse):
         return 20.0 * np.log10(1.0 / np.sqrt(mse))
 
 
-def _device_sums(model, cameras, bg, masks, mode_bits: int, want_ssim: bool, batch: int, capacity=None, lpips_weights=None):
-    """-> (sums [N, 2C+2] float64, ssim [N] or None, H*W per view, lpips [N] or None), one read-back at the end."""
+def _fit_views(imgs, gts, mk):
+    """Every render through the best affine colour map onto its ground truth (exposure.fit_exposure over the pixels of the
+    view's mask; a degenerate view keeps the identity) -> (the fitted renders, the matrices).  No host read."""
+    from .exposure import apply_exposure_batch, fit_exposure
+    planes = None if mk is None else [None if m is None else (m[0] != 0).to(torch.uint8) for m in mk]
+    fits = fit_exposure([x.contiguous() for x in imgs], [g.to(imgs[0].device, torch.float32).contiguous() for g in gts], planes)
+    with torch.no_grad():
+        out = apply_exposure_batch([x.contiguous() for x in imgs], [A for A, _ in fits])
+    return out, [A for A, _ in fits]
+
+
+def _device_sums(model, cameras, bg, masks, mode_bits: int, want_ssim: bool, batch: int, capacity=None, lpips_weights=None,
+                 fitted=None):
+    """-> (sums [N, 2C+2] float64, ssim [N] or None, H*W per view, lpips [N] or None), one read-back at the end.
+    `fitted`: a list that receives (view index, its fitted 3x4 on the device); the renders are then scored after _fit_views."""
     from . import _C
     parts = []
     lp = []
     for idx, imgs in _batches(model, cameras, bg, batch, capacity):
         gts = [cameras[i].original_image for i in idx]
         mk = None if masks is None else [masks[i] for i in idx]
+        if fitted is not None:
+            imgs, mats = _fit_views(imgs, gts, mk)
+            fitted.extend(zip(idx, mats))
         sums, pi, pg = image_metrics(imgs, gts, mk, mode_bits, prepared=want_ssim)
         ss = _C.ssim(pi, pg, 11, False) if want_ssim else None
         if lpips_weights is not None:        # metrics.py:105 on the pair of metrics.py:95-96
@@ -165,7 +181,7 @@ def _device_sums(model, cameras, bg, masks, mode_bits: int, want_ssim: bool, bat
 
 
 def evaluate_views(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, mode: str = "report",
-                   batch: int = MAX_BATCH, lpips_weights=None) -> dict:
+                   batch: int = MAX_BATCH, lpips_weights=None, fit_exposure: bool = False) -> dict:
     """SSIM / PSNR / L1 of every camera's render against its `original_image`.
 
     mode "report": both images clamped to [0,1]; PSNR = mean of the per-channel PSNRs (train.py:226-261).
@@ -174,12 +190,16 @@ def evaluate_views(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, mo
     SSIM is ssim() of the composited pair, L1 the mean |difference| of the same pair.
     `lpips_weights` (lpips.LpipsWeights): every per-view dict also gets "LPIPS" = lpips(net_type='vgg') of that same pair
     (metrics.py:105) and the result its fp32 mean; SSIM, PSNR and L1 keep their bits.
+    `fit_exposure`: every render is first mapped onto its ground truth by the best 3x4 affine colour map (the colour-corrected
+    metrics of RawNeRF / Zip-NeRF: exposure.fit_exposure, over the view's mask where it has one); every per-view dict gains
+    "exposure", the fitted matrix.
     -> {"per_view": [{"SSIM", "PSNR", "L1"}, ...], "SSIM", "PSNR", "L1": fp32 means of the per-view values}."""
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}")
     if not cameras:
         return {"per_view": [], "SSIM": math.nan, "PSNR": math.nan, "L1": math.nan}
-    sums, ssim, hw, lp = _device_sums(model, cameras, bg, masks, MODES[mode], True, batch, lpips_weights=lpips_weights)
+    fitted = [] if fit_exposure else None
+    sums, ssim, hw, lp = _device_sums(model, cameras, bg, masks, MODES[mode], True, batch, lpips_weights=lpips_weights, fitted=fitted)
     C = (sums.shape[1] - 2) // 2
     l1 = sums[:, :C].sum(1) / (C * hw)
     if mode == "report":
@@ -190,6 +210,10 @@ def evaluate_views(model, cameras: Sequence, bg: torch.Tensor, *, masks=None, mo
     if lp is not None:
         for v, x in zip(per_view, lp):
             v["LPIPS"] = float(x)
+    if fitted:
+        mats = torch.stack([A for _, A in fitted]).cpu().tolist()
+        for (i, _), A in zip(fitted, mats):
+            per_view[i]["exposure"] = A
     res = {"per_view": per_view}
     for key in ("SSIM", "PSNR", "L1") + (("LPIPS",) if lp is not None else ()):     # metrics.py:108-110: torch.tensor(values).mean() -- fp32
         res[key] = float(torch.tensor([v[key] for v in per_view]).mean())
@@ -249,21 +273,26 @@ def depth_pearson(model, cameras: Sequence, bg: torch.Tensor, priors_dir: str, m
 
 # ---- results.json / per_view.json (metrics.py:105-122) ----------------------------------------------------------------
 def write_results(model_path: str, method: str, per_view: Sequence[dict], names: Sequence[str], aligned: Optional[Sequence[dict]] = None,
-                  twists=None) -> dict:
+                  twists=None, exposure: Optional[Sequence[dict]] = None) -> dict:
     """Writes <model_path>/results.json {method: {"SSIM", "PSNR"}} and per_view.json {method: {"SSIM": {name: v}, "PSNR":
     {name: v}}} in the reference's layout (json.dump, indent=True); the "LPIPS" key is written in both files, as
     metrics.py:112-117 does, when EVERY per-view entry carries it, and left out otherwise; so is "DepthPearson" (depth_pearson).  Means are fp32, as
     torch.tensor(values).mean() is there.  `aligned` (the per-view metrics after pose alignment) adds the same keys with the
     suffix _aligned behind them, `twists` ([n,6]) adds per_view.json's "twist": {name: [omega, t]}; without them the files are
-    what they were.  Returns the two dicts."""
-    if len(per_view) != len(names) or (aligned is not None and len(aligned) != len(names)):
+    what they were.  `exposure` (the per-view metrics after evaluate_views(fit_exposure=True)) adds the keys with the suffix
+    _exposure in the same way and per_view.json's "exposure": {name: 3x4}.  Returns the two dicts."""
+    if len(per_view) != len(names) or any(x is not None and len(x) != len(names) for x in (aligned, exposure)):
         raise ValueError("one name per view")
     keys = ("SSIM", "PSNR") + tuple(k for k in ("LPIPS", "DepthPearson") if per_view and all(k in v for v in per_view))
     vals = {k: torch.tensor([float(v[k]) for v in per_view]) for k in keys}
     if aligned is not None:
         vals.update({k + "_aligned": torch.tensor([float(v[k]) for v in aligned]) for k in keys if all(k in v for v in aligned)})
+    if exposure is not None:
+        vals.update({k + "_exposure": torch.tensor([float(v[k]) for v in exposure]) for k in keys if all(k in v for v in exposure)})
     full = {method: {k: vals[k].mean().item() for k in vals}}
     per = {method: {k: {name: x for x, name in zip(vals[k].tolist(), names)} for k in vals}}
+    if exposure is not None:
+        per[method]["exposure"] = {name: v["exposure"] for v, name in zip(exposure, names)}
     if twists is not None:
         per[method]["twist"] = {name: [float(x) for x in t] for t, name in zip(twists, names)}
     os.makedirs(model_path, exist_ok=True)
@@ -277,14 +306,17 @@ def write_results(model_path: str, method: str, per_view: Sequence[dict], names:
 # ---- command line: metrics.py over the test cameras of a trained model ------------------------------------------------
 def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1, mode: str = "png", lpips_weights=None,
         masks=None, align_poses: int = 0, align_scales: Sequence[int] = (4, 2, 1), depth_priors: Optional[str] = None,
-        depth_prior_mode: Optional[str] = None) -> dict:
+        depth_prior_mode: Optional[str] = None, fit_exposure: bool = False) -> dict:
     """Loads <model_path>/point_cloud/iteration_<it> and the dataset's test cameras (cfg_args gives the defaults, as in
     spiral.py), evaluates them, prints the means in metrics.py:107-109's format and writes results.json / per_view.json under
     method ours_<it>.  `masks`: DTU IDR object masks per test camera (the command line does not read them).
     align_poses = N > 0: the cameras are refined for N iterations each (pose.refine_poses, coarse to fine over align_scales)
     and evaluated again; the result gains "aligned" (evaluate_views of the refined cameras) and "twists".
     depth_priors = DIR: "DepthPearson", the mean rho_image against <DIR>/<image_name>.npy of the test views (depth_pearson;
-    depth_prior_mode defaults to the run's own in cfg_args), in results.json and per view in per_view.json."""
+    depth_prior_mode defaults to the run's own in cfg_args), in results.json and per view in per_view.json.
+    fit_exposure: the views are scored a second time after the best affine colour map onto their ground truth (a held-out
+    view has no learned exposure); the result gains "exposure" and the files SSIM_exposure / PSNR_exposure / LPIPS_exposure
+    and each view's matrix."""
     from .gaussian_model import GaussianModel
     from .scene import Scene
     from .spiral import max_iteration, read_cfg_args
@@ -317,6 +349,15 @@ def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1,
         print("  DepthPearson: {:>12.7f}".format(res["DepthPearson"]))
     print("")
     names = ["{0:05d}.png".format(i) for i in range(len(cams))]      # render.py:34: the file names metrics.py lists
+    fit = None
+    if fit_exposure:
+        res["exposure"] = evaluate_views(model, cams, bg, masks=masks, mode=mode, lpips_weights=lpips_weights, fit_exposure=True)
+        fit = res["exposure"]["per_view"]
+        print("  SSIM (exposure): {:>12.7f}".format(res["exposure"]["SSIM"]))
+        print("  PSNR (exposure): {:>12.7f}".format(res["exposure"]["PSNR"]))
+        if "LPIPS" in res["exposure"]:
+            print("  LPIPS (exposure): {:>12.7f}".format(res["exposure"]["LPIPS"]))
+        print("")
     if align_poses > 0:
         from .pose import refine_poses
         refined, twists, _ = refine_poses(model, cams, masks=masks, iters=int(align_poses), scales=tuple(align_scales), bg=bg)
@@ -327,9 +368,9 @@ def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1,
         if "LPIPS" in res["aligned"]:
             print("  LPIPS (aligned): {:>12.7f}".format(res["aligned"]["LPIPS"]))
         print("")
-        write_results(model_path, "ours_{}".format(it), res["per_view"], names, res["aligned"]["per_view"], twists)
+        write_results(model_path, "ours_{}".format(it), res["per_view"], names, res["aligned"]["per_view"], twists, exposure=fit)
         return res
-    write_results(model_path, "ours_{}".format(it), res["per_view"], names)
+    write_results(model_path, "ours_{}".format(it), res["per_view"], names, exposure=fit)
     return res
 
 
@@ -349,6 +390,9 @@ def main(argv=None) -> int:
     p.add_argument("--depth_priors", default=None, metavar="DIR",
                    help="<image_name>.npy priors of the test views: adds DepthPearson (mean rho_image) to results.json / per_view.json")
     p.add_argument("--depth_prior_mode", choices=("depth", "disparity"), default=None, help="default: the training run's")
+    p.add_argument("--fit_exposure", action="store_true",
+                   help="score every view again after the best 3x4 affine colour map onto its ground truth: SSIM_exposure / "
+                        "PSNR_exposure / LPIPS_exposure in results.json, each view's matrix in per_view.json")
     a = p.parse_args(argv)
     w = None
     if a.lpips_npz:
@@ -362,7 +406,7 @@ def main(argv=None) -> int:
         from .lpips import load_weights
         w = load_weights(a.lpips_vgg, a.lpips_lin)
     run(a.model_path, a.source_path, a.iteration, a.mode, w, align_poses=a.align_poses, align_scales=a.align_scales,
-        depth_priors=a.depth_priors, depth_prior_mode=a.depth_prior_mode)
+        depth_priors=a.depth_priors, depth_prior_mode=a.depth_prior_mode, fit_exposure=a.fit_exposure)
     return 0
 
 

@@ -13,13 +13,17 @@ What a captured graph fixes, and where each per-iteration value therefore lives
     the depth prior, its validity, the       copied into static buffers next to the mask; the patch offsets: two int32 words
     patch offsets (depth_prior.PriorTerm)    (PriorTerm.offset_buffer) the kernels read, one pinned upload per draw
     the learning rates                       six floats of the same block (B3gsAdamSegment::lr_dev), one pinned upload
+    the exposure row and its learning rate   two words of exposure.ExposureTerm's own block (the table, the moments, the step
+    (exposure.ExposureTerm)                  counts are static too), one pinned upload; the kernels read the row on the device
 No value is read back inside an iteration.
 
 What cannot live in device memory is a SHAPE of the graph, captured at its first use and kept:
-    (pair?, opacity decay factor of the Adam launch or 0, statistics on?, mask kind[, "prior"])
+    (pair?, opacity decay factor of the Adam launch or 0, statistics on?, mask kind[, "prior"][, "exposure"])
 -- single view while `it <= shift_cam_start` or `binocular` is off, the (input, shifted) pair with one depth sort afterwards;
 the fifth entry is there while the depth-prior term is active (all training views carry a prior, or none: a mixed set is
-refused) and ABSENT otherwise, so a run without priors has the keys, the events and the launches it always had;
+refused) and ABSENT otherwise, so a run without priors has the keys, the events and the launches it always had; a trailing
+"exposure" is there, in the same way, only while the exposure term is active: the replay then applies the drawn view's row to
+the render (and the shifted partner's) in one launch, and runs the row's Adam behind the fused step under the same capacity word;
 the decay switches on once (`it > densify_from_iter`), the statistics switch off once (`it >= densify_until_iter`, only with
 the decay off: with it on, densification runs to the end).  These windows are schedule.TrainerBase.plan, the one place
 that decides them for both trainers; "the replay carries Adam" is its `step and not densify`.  Every kept graph is dropped, and captured
@@ -76,7 +80,8 @@ class _Captured:
 class FusedBackend:
     """The device side of GraphTrainer: static storage, the step objects, capture and the capacity word."""
 
-    def __init__(self, model, views, background, lambda_dssim=0.2, smooth_weight=0.05, binning_capacity=None, depth_prior=None):
+    def __init__(self, model, views, background, lambda_dssim=0.2, smooth_weight=0.05, binning_capacity=None, depth_prior=None,
+                 exposure=None):
         from . import _lib, checkpoint
         from .camera import CameraPairSlots, _PinnedRing
         from .fused import FusedRasterizer
@@ -124,6 +129,10 @@ class FusedBackend:
             self.prior_mask = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
             self.offset_dev = self.prior_term.offset_buffer(dev)
         self._prior = False
+        # exposure.ExposureTerm: its table, moments, row word and learning rate are static device memory of its own
+        self.exposure_term = exposure
+        self.has_exposure = exposure is not None
+        self._exposure = False
         self.fused = FusedRasterizer(model, W, H, num_slots=2, want_means2D=False, binning_capacity=binning_capacity)
         self.st = ViewShardedStep(model, [(self.slots.cam, self.slots.shifted, 0.1)], self.bg, optimizer=self.opt,
                                   fused=self.fused, overflow_check_every=0)
@@ -144,10 +153,12 @@ class FusedBackend:
         kind = d.key[3]
         if kind is not None:
             self.mask.copy_(cam.gt_alpha_mask if kind == "alpha" else cam.bg_mask, non_blocking=True)
-        if len(d.key) > 4:
+        if "prior" in d.key[4:]:
             self.prior.copy_(cam.depth_prior, non_blocking=True)
             self.prior_mask.copy_(cam.depth_prior_mask, non_blocking=True)
             self.prior_term.upload_offset(d.offset, self.offset_dev.device)
+        if "exposure" in d.key[4:]:
+            self.exposure_term.stage(d.view, d.it)
         if d.bg is not self._bg_src:
             self.bg.copy_(d.bg, non_blocking=True)
             self._bg_src = d.bg
@@ -160,7 +171,7 @@ class FusedBackend:
 
     def _configure(self, key):
         pair, decay, stats, kind = key[:4]
-        self._prior = len(key) > 4
+        self._prior, self._exposure = "prior" in key[4:], "exposure" in key[4:]
         v0, v1 = self._both
         self.st.views = [v0, v1] if pair else [v0]
         v0.mate = 1 if pair else None
@@ -171,8 +182,14 @@ class FusedBackend:
     def _loss_fn(self, i, cam, pkg, spkg, t):
         from .fused_loss import binocular_loss_fused
         pair, kind = self._pair, self._kind
-        total = binocular_loss_fused(pkg["render"], pkg["rendered_depth"], pkg["rendered_alpha"], self.gt,
-                                     lambda_dssim=self.lam, shifted_image=spkg["render"] if pair else None,
+        image, shifted = pkg["render"], spkg["render"] if pair else None
+        if self._exposure:      # the staged row, one apply launch (and one backward launch) for the pair
+            if pair:
+                image, shifted = self.exposure_term.apply(None, image, shifted)
+            else:
+                image = self.exposure_term.apply(None, image)
+        total = binocular_loss_fused(image, pkg["rendered_depth"], pkg["rendered_alpha"], self.gt,
+                                     lambda_dssim=self.lam, shifted_image=shifted,
                                      focal_x=self.focal_x, trans_dist=0.0 if pair else None,
                                      trans_dist_dev=self.slots.trans_dist_dev if pair else None,
                                      gt_alpha_mask=self.mask if kind == "alpha" else None,
@@ -185,21 +202,29 @@ class FusedBackend:
 
     def _state(self):
         m, o = self.model, self.opt
-        return list(m.parameters()) + [o.exp_avg, o.exp_avg_sq, o._step_words, m.xyz_gradient_accum, m.denom, m.max_radii2D]
+        own = self.exposure_term.state() if self.has_exposure else []
+        return list(m.parameters()) + [o.exp_avg, o.exp_avg_sq, o._step_words, m.xyz_gradient_accum, m.denom, m.max_radii2D] + own
+
+    def _step(self):
+        """One full step: the fused step, then (while the term is active) the exposure row's Adam under the same capacity
+        word -- an overflowing iteration drops both, and settle() repeats both."""
+        self.st.step(loss_fn=self._loss_fn)
+        if self._exposure:
+            self.exposure_term.adam(self.fused.overflow_flag)
 
     def capture(self, key) -> _Captured:
         """Warm-up steps (they settle every allocation; the last one on a side stream, as a capture wants it), the capture,
         and the state the warm-up moved put back: capturing an iteration does not train."""
         self._configure(key)
-        st, dev = self.st, self.model.get_xyz.device
+        dev = self.model.get_xyz.device
         with torch.no_grad():
             snap = [t.detach().clone() for t in self._state()]
-        st.step(loss_fn=self._loss_fn)
+        self._step()
         torch.cuda.synchronize(dev)
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            st.step(loss_fn=self._loss_fn)
+            self._step()
         torch.cuda.current_stream(dev).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         # The cyclic collector runs before the capture and stays out of it: a finaliser it ran there could make a call a
@@ -211,7 +236,7 @@ class FusedBackend:
         gc.disable()
         try:
             with torch.cuda.graph(graph):
-                st.step(loss_fn=self._loss_fn)
+                self._step()
         finally:
             if collecting:
                 gc.enable()
@@ -263,7 +288,8 @@ class GraphTrainer(TrainerBase):
         self.save_iterations, self.checkpoint_iterations = frozenset(save_iterations), frozenset(checkpoint_iterations)
         self.check_every = int(check_every)
         self.backend = backend if backend is not None else FusedBackend(model, self.views, background, self.lam,
-                                                                        self.smooth_weight, binning_capacity, self.depth_prior)
+                                                                        self.smooth_weight, binning_capacity, self.depth_prior,
+                                                                        self.exposure)
         self.events = events
         self.captures = 0        # graphs captured so far: a replay does not move it
         self.grown = 0           # capacity events settled
@@ -347,6 +373,8 @@ class GraphTrainer(TrainerBase):
         offset = None
         if getattr(b, "has_prior", False) and self.depth_prior.active(it):
             key, offset = key + ("prior",), self.depth_prior.draw_offset()      # (the term's own generator; kept for a repeat)
+        if getattr(b, "has_exposure", False) and self.exposure.active(it):
+            key = key + ("exposure",)
         self._run(Draw(it, view_index, float(shift) if plan.pair else None, self.background, lr, key, adam, offset))
         self.densified = False
         if not adam:

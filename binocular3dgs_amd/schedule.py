@@ -58,7 +58,7 @@ class TrainerBase:
                  opacity_decay_factor=0.995, lambda_dssim=0.2, densify_from_iter=500, densify_until_iter=15_000,
                  densification_interval=100, densify_grad_threshold=0.0002, min_opacity=0.005, sh_interval=1000,
                  smooth_weight=0.05, before_densify=None, test_cameras=None, test_iterations=(), report_fn=None,
-                 after_report=None, depth_prior=None):
+                 after_report=None, depth_prior=None, exposure=None):
         self.model, self.scene, self.pipe, self.background = model, scene, pipe, background
         self.iterations, self.shift_cam_start, self.binocular = iterations, shift_cam_start, binocular
         self.decay, self.lam, self.smooth_weight = opacity_decay_factor, lambda_dssim, smooth_weight
@@ -71,6 +71,9 @@ class TrainerBase:
         self.report_fn, self.reports = report_fn, {}
         # depth_prior.PriorTerm or None: a view that carries a `depth_prior` adds the Pearson depth term to the total
         self.depth_prior = depth_prior
+        # exposure.ExposureTerm or None: the drawn view's render (and its shifted partner's) goes through the view's learned
+        # 3x4 colour transform before the loss; None leaves every call, event and launch as it was
+        self.exposure = exposure
         self.after_report = after_report    # called with the iteration at train.py:166-169 (the point where it saves)
         self.views = list(scene.getTrainCameras())
         self.densified = False      # did the iteration just run change the Gaussian set?
@@ -121,11 +124,16 @@ class IterationSchedule(TrainerBase):
         self.ema = 0.0
 
     # ---- the terms of the loss --------------------------------------------------------------------------------------
-    def _stereo_term(self, cam, first, target, shift):
-        """Render the partner `shift` along the camera's x axis, warp it back with the primary's depth, compare."""
+    def _stereo_term(self, cam, first, target, shift, expose=None):
+        """Render the partner `shift` along the camera's x axis, warp it back with the primary's depth, compare.
+        `expose`: (first render, partner render) -> the two through the view's exposure row (both are compared with the same
+        photo); the first is then left in `self._exposed` for the photometric terms."""
         ops = self.ops
         partner = self.scene.getShiftedCamera(cam, shift)
         second = ops.render(partner, self.model, self.pipe, self.background)
+        if expose is not None:
+            self._exposed, shifted = expose(first["render"], second["render"])
+            second = dict(second, render=shifted)
         fx = cam.get_focal()[0]
         disp = (fx * -shift) / (first["rendered_depth"] + 1e-5)
         disp4, target4 = disp[None], target[None]
@@ -149,14 +157,23 @@ class IterationSchedule(TrainerBase):
         first = ops.render(cam, m, self.pipe, self.background)
         target = cam.original_image.to(self.background.device)
         stereo = 0.0
-        if plan.pair:
+        # the exposure term (active from its `from_iter`): ONE apply for the render and its shifted partner, whose gradient
+        # sums for the view's matrix meet in fp64
+        expo = self.exposure if (self.exposure is not None and self.exposure.active(it)) else None
+        image = first["render"]
+        if plan.pair and expo is not None:
+            stereo = self._stereo_term(cam, first, target, float(shift), lambda a, b: expo.apply(view_index, a, b))
+            image = self._exposed
+        elif plan.pair:
             stereo = self._stereo_term(cam, first, target, float(shift))
+        elif expo is not None:
+            image = expo.apply(view_index, image)
         coverage = 0.0
         kind = mask_kind(cam)
         if kind is not None:
             coverage = (first["rendered_alpha"].abs() * ((1 - cam.gt_alpha_mask) if kind == "alpha" else cam.bg_mask)).mean()
-        photo = ops.l1_loss(first["render"], target)
-        recon = (1.0 - self.lam) * photo + self.lam * (1.0 - ops.ssim(first["render"], target))
+        photo = ops.l1_loss(image, target)
+        recon = (1.0 - self.lam) * photo + self.lam * (1.0 - ops.ssim(image, target))
         total = self._add_loss_terms(recon + stereo + coverage)
         if self.depth_prior is not None:
             total = self.depth_prior.add(total, it, cam, first)
@@ -191,6 +208,10 @@ class IterationSchedule(TrainerBase):
             opt.step()
             opt.zero_grad(set_to_none=True)
             self._after_step(it, lr_xyz)
+            # the exposure row's own Adam, on the iterations whose optimiser step carries gradients (graph_trainer: the
+            # replayed ones): not on a densification iteration, not on the last one
+            if self.exposure is not None and self.exposure.active(it) and not plan.densify:
+                self.exposure.step(it)
 
     def _densify(self, it):
         self.model.densify_and_prune(self.grad_threshold, self.min_opacity, self.scene.cameras_extent, None)

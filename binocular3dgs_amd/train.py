@@ -14,6 +14,10 @@ The reference's train.py: a COLMAP / Blender dataset folder in, a trained model 
     --depth_priors DIR     <image_name>.npy depth (or inverse-depth) priors of the training views: the Pearson depth loss of
                            depth_prior.py (both --step modes; --depth_prior_mode depth|disparity, --depth_prior_weight, --depth_prior_local with
                            --depth_prior_patch, --depth_prior_from / --depth_prior_until, --depth_prior_alpha_min)
+    --exposure             a learned 3x4 affine colour transform per training image (exposure.ExposureTerm: upstream 3DGS's
+                           exposure compensation), applied to the render before the loss; --exposure_lr_init / --exposure_lr_final,
+                           --exposure_from IT; exposure.json next to every saved point cloud, chkpnt<n>.exposure.pth next to
+                           every checkpoint (the reference's checkpoint tuple is untouched)
     --densify adc|mcmc     adc (default): the reference's clone / split / prune; mcmc: mcmc.McmcSchedule -- relocation, growth to
                            --cap_max and position noise (--noise_lr, --opacity_reg, --scale_reg); --step schedule only
 
@@ -100,7 +104,17 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--depth_prior_from", type=int, default=0)
     p.add_argument("--depth_prior_until", type=int, default=None)
     p.add_argument("--depth_prior_alpha_min", type=float, default=0.0, help="pixels with rendered alpha below this are not used")
+    p.add_argument("--exposure", action="store_true", help="learn a 3x4 affine colour transform per training image")
+    p.add_argument("--exposure_lr_init", type=float, default=0.01)
+    p.add_argument("--exposure_lr_final", type=float, default=0.001)
+    p.add_argument("--exposure_from", type=int, default=0, metavar="IT", help="the first iteration the transform is applied in")
     return p
+
+
+def exposure_sidecar(checkpoint_path: str) -> str:
+    """chkpnt<n>.pth -> chkpnt<n>.exposure.pth"""
+    root, ext = os.path.splitext(checkpoint_path)
+    return root + ".exposure" + (ext or ".pth")
 
 
 def check_args(args) -> None:
@@ -110,6 +124,13 @@ def check_args(args) -> None:
         raise ValueError("--depth_prior_weight / --depth_prior_local need --depth_priors DIR, the folder of the priors")
     if wl != 0.0 and not 8 <= getattr(args, "depth_prior_patch", 64) <= 256:
         raise ValueError("--depth_prior_local needs --depth_prior_patch in 8 .. 256")
+    if getattr(args, "exposure", False):
+        if not (getattr(args, "exposure_lr_init", 0.01) > 0.0 and getattr(args, "exposure_lr_final", 0.001) > 0.0):
+            raise ValueError("--exposure_lr_init and --exposure_lr_final are > 0 (the schedule is log-linear)")
+        if getattr(args, "exposure_from", 0) < 0:
+            raise ValueError("--exposure_from IT needs IT >= 0")
+    elif any(getattr(args, k, d) != d for k, d in (("exposure_lr_init", 0.01), ("exposure_lr_final", 0.001), ("exposure_from", 0))):
+        raise ValueError("--exposure_lr_init / --exposure_lr_final / --exposure_from need --exposure")
     if getattr(args, "densify", "adc") != "mcmc":
         return
     if getattr(args, "cap_max", None) is None or args.cap_max < 1:
@@ -159,6 +180,14 @@ def run(args) -> dict:
         model_params, first_iter = checkpoint.load(args.start_checkpoint)
         model.restore(model_params, args)
     background = torch.tensor([1, 1, 1] if args.white_background else [0, 0, 0], dtype=torch.float32, device=dev)
+    exposure = None
+    if getattr(args, "exposure", False):
+        from .exposure import ExposureTerm
+        exposure = ExposureTerm([c.image_name for c in scene.getTrainCameras()], device=dev, lr_init=args.exposure_lr_init,
+                                lr_final=args.exposure_lr_final, iterations=args.iterations, from_iter=args.exposure_from)
+        # (a checkpoint written without --exposure has no sidecar: the term then starts from the identity)
+        if args.start_checkpoint and os.path.isfile(exposure_sidecar(args.start_checkpoint)):
+            exposure.load_state_dict(torch.load(exposure_sidecar(args.start_checkpoint), map_location="cpu"))
 
     def after_report(it):
         # (`reports`, not the trainer: a closure that named its trainer would tie the two into a reference cycle, and the
@@ -168,6 +197,10 @@ def run(args) -> dict:
         if it in args.save_iterations:
             say("\n[ITER {}] Saving Gaussians".format(it))
             scene.save(it)
+            if exposure is not None:
+                from .exposure import write_matrices
+                write_matrices(os.path.join(args.model_path, "point_cloud", "iteration_{}".format(it), "exposure.json"),
+                               exposure.matrices())
 
     kw = dict(iterations=args.iterations, shift_cam_start=args.shift_cam_start, binocular=args.binocular_consistency,
               opacity_decay_factor=args.opacity_decay_factor if args.opacity_decay else None,
@@ -181,6 +214,8 @@ def run(args) -> dict:
         kw["depth_prior"] = PriorTerm(mode=args.depth_prior_mode, weight=args.depth_prior_weight, local=args.depth_prior_local,
                                       patch=args.depth_prior_patch, from_iter=args.depth_prior_from, until_iter=args.depth_prior_until,
                                       alpha_min=args.depth_prior_alpha_min, seed=args.seed)
+    if exposure is not None:
+        kw["exposure"] = exposure
     if getattr(args, "step", "schedule") == "graph":
         from .graph_trainer import GraphTrainer
         sched = GraphTrainer(model, scene, PipelineParams(), background, save_iterations=args.save_iterations,
@@ -205,11 +240,13 @@ def run(args) -> dict:
         if it in args.checkpoint_iterations:
             say("\n[ITER {}] Saving Checkpoint".format(it))
             checkpoint.save(args.model_path + "/chkpnt" + str(it) + ".pth", model, model.optimizer, it)
+            if exposure is not None:
+                torch.save(exposure.state_dict(), exposure_sidecar(args.model_path + "/chkpnt" + str(it) + ".pth"))
     sched.settle()
     say("\nTraining complete.")
     return {"model_path": args.model_path, "first_iteration": first_iter + 1, "iterations": args.iterations,
             "loss": None if loss is None else float(loss.detach()), "points": int(model.get_xyz.shape[0]), "reports": dict(sched.reports),
-            "scene": scene, "model": model, "captures": sched.captures, "trainer": sched}
+            "scene": scene, "model": model, "captures": sched.captures, "trainer": sched, "exposure": exposure}
 
 
 def main(argv=None) -> int:

@@ -1723,6 +1723,78 @@ size_t b3gs_depth_prior_workspace_bytes(int32_t W, int32_t H, int32_t patch);
 int b3gs_depth_prior_loss_batch(int32_t n_views, const B3gsDepthPriorIO* io, b3gs_stream_t stream);
 int b3gs_resize_depth_batch(int32_t n_views, const B3gsDepthResizeIO* io, b3gs_stream_t stream);
 
+/* ---- per-image exposure compensation (added to ABI 18; csrc/exposure.hip, binocular3dgs_amd/exposure.py, INTEGRATION.md
+ * section 31) --------------------------------------------------------------------------------------------------------------
+ * Five entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * tests/exposure_ref.py restates every rule below in numpy float64.
+ *
+ * The transform of an image x = (r, g, b) [3, H, W] by a matrix A [3, 4] (12 floats, row-major; row c = [a_c0 a_c1 a_c2 t_c]):
+ *      out_c = t_c + a_c0 r + a_c1 g + a_c2 b,  c = 0, 1, 2;  no clamp;  the identity is [I | 0].
+ * All arithmetic is fp64, only + - * / sqrt, every statement one rounded operation in the order written; a float32 result is
+ * rounded once.  A plane names its matrix as 12 floats (row_dev NULL), or as a table [V, 12] and a device word *row_dev: the
+ * kernels read the word (clamped to [0, V - 1]), so a captured launch follows it.
+ * The TREE of 256 values, and the FOLD of partials, are those of the depth-prior section above: the xor butterfly per group of
+ * 64 and (g0 + g1) + (g2 + g3); s[l] = the partials l, l + 64, .. added in that order to +0, then the butterfly of s[0..63].
+ * Block b of a plane holds pixels 256 b .. 256 b + 255 (row-major); a pixel outside the image, or not used, enters as +0.
+ *
+ * 1. b3gs_exposure_apply: out_c = (float)(((t_c + a_c0 r) + a_c1 g) + a_c2 b).  One launch for up to 8 planes of any sizes.
+ *    `g_out`, `G` and `workspace` are not read.
+ * 2. b3gs_exposure_backward: `out` receives g_in_k = (float)((A[0][k] g0 + A[1][k] g1) + A[2][k] g2), g = g_out; and
+ *      G[c][k] = sum over the pixels of g_c x_k (k < 3),  G[c][3] = sum of g_c
+ *    as the TREE per block and the FOLD of a plane's partials.  Planes SHARE a matrix when they name the same `A` and the same
+ *    `row_dev`; they must then name the same `G`, and get ONE combined G: the folds of the planes added in plane order to +0
+ *    (a trainer's input view and its shifted partner are such a pair: their sum is never formed in float32).  `G`: 12 doubles
+ *    followed by their 12 float32 roundings (144 bytes), written by the last workgroup of the group to arrive.  One launch.
+ * 3. b3gs_exposure_fit: per plane, over the pixels with mask != 0 (all when mask is NULL), with x = (r, g, b, 1) of the
+ *    render and y = the ground truth,
+ *      S = sum x x^T  (its 10 unique entries in the order rr rg rb r gg gb g bb b n),  B[c][i] = sum x_i y_c,
+ *    TREE and FOLD as above; `sums` = [n, the 10 of S, the 12 of B] (23 doubles; n is S's last entry).  Then S a_c = B[c]:
+ *      for j = 0..3:  d = S[j][j] - L[j][0]^2 - .. - L[j][j-1]^2 (left to right);  L[j][j] = sqrt(d);
+ *                     for i > j:  L[i][j] = (S[i][j] - L[i][0] L[j][0] - .. - L[i][j-1] L[j][j-1]) / L[j][j]
+ *      y_i = (B[c][i] - L[i][0] y_0 - .. ) / L[i][i], i = 0..3;   a_i = (y_i - L[i+1][i] a_{i+1} - .. - L[3][i] a_3) / L[i][i], i = 3..0
+ *    and A[c] = (float)(a_0, a_1, a_2, a_3).  DEGENERATE: n < 16, or a pivot d that is not > 2^-40 trace(S), trace =
+ *    ((rr + gg) + bb) + n: then A is the identity and *flag = 1; otherwise *flag = 0.  One launch, no host read.
+ * 4. b3gs_exposure_adam: Adam on ONE row of the table, row = *row_dev (outside [0, V): nothing happens), one launch of 12
+ *    lanes.  prods [V, 2] holds the running products beta1^t, beta2^t of every row (1 before its first step), steps [V] its t:
+ *      p1 = prods[row][0] beta1, p2 = prods[row][1] beta2 (stored back), steps[row] += 1,
+ *      m = beta1 m + (1 - beta1) g,  v = beta2 v + ((1 - beta2) g) g  (stored as float32),
+ *      x = (float)(x - (lr (m / (1 - p1))) / (sqrt(v) / sqrt(1 - p2) + eps))
+ *    with g = grad[k] (12 doubles: a G), lr = *lr_dev, m and v the unrounded values.  Only the named row moves: the rows of
+ *    views that were not drawn do not drift on their momentum.  While *skip_if_nonzero != 0 (NULL: never) the launch returns
+ *    at once -- the sticky capacity word that b3gs_adam_step obeys.
+ * `workspace`: b3gs_exposure_workspace_bytes(W, H) bytes (0 for sizes that are refused: 1 <= W, H and W H <= 2^24), 256-byte
+ * aligned, one per plane, ZERO before its first use; a call leaves it ready for the next one (the arrival counters at its head
+ * reset themselves).  Bad arguments are B3GS_ERR_ARG before the first HIP call. */
+#define B3GS_EXPOSURE_MAX_PLANES 8
+typedef struct B3gsExposurePlane {
+  int32_t W, H;
+  const float* in;             /* [3, H, W] */
+  const float* g_out;          /* backward: [3, H, W] */
+  float* out;                  /* apply: the transformed image; backward: g_in; [3, H, W], every word written */
+  const float* A;              /* 12 floats, or the table [V, 12] when row_dev is given */
+  const int32_t* row_dev;      /* NULL, or one word on the device */
+  int32_t V;                   /* rows of the table */
+  double* G;                   /* backward: 12 doubles + 12 floats on the device */
+  void* workspace;             /* backward */
+} B3gsExposurePlane;
+typedef struct B3gsExposureFitIO {
+  int32_t W, H;
+  const float* render;         /* [3, H, W] */
+  const float* gt;             /* [3, H, W] */
+  const uint8_t* mask;         /* NULL, or [H, W] */
+  float* A;                    /* [12] on the device */
+  double* sums;                /* [23] on the device */
+  int32_t* flag;               /* one word on the device */
+  void* workspace;
+} B3gsExposureFitIO;
+size_t b3gs_exposure_workspace_bytes(int32_t W, int32_t H);
+int b3gs_exposure_apply(int32_t n_planes, const B3gsExposurePlane* io, b3gs_stream_t stream);
+int b3gs_exposure_backward(int32_t n_planes, const B3gsExposurePlane* io, b3gs_stream_t stream);
+int b3gs_exposure_fit(int32_t n_planes, const B3gsExposureFitIO* io, b3gs_stream_t stream);
+int b3gs_exposure_adam(int32_t V, float* table, float* exp_avg, float* exp_avg_sq, int32_t* steps, double* prods,
+                       const int32_t* row_dev, const double* grad, const float* lr_dev, double beta1, double beta2, double eps,
+                       const int32_t* skip_if_nonzero, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
