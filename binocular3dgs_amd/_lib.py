@@ -223,6 +223,24 @@ class B3gsExposureFitIO(C.Structure):
                 ("sums", C.c_void_p), ("flag", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class B3gsNormalPriorIO(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("depth", C.c_void_p), ("alpha", C.c_void_p), ("target", C.c_void_p),
+                ("mask", C.c_void_p), ("alpha_min", C.c_float), ("tanfovx", C.c_double), ("tanfovy", C.c_double),
+                ("w_cos", C.c_double), ("w_l1", C.c_double), ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p),
+                ("normals", C.c_void_p), ("valid", C.c_void_p), ("parts", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+class B3gsDepthNormalsIO(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("depth", C.c_void_p), ("alpha", C.c_void_p), ("mask", C.c_void_p),
+                ("alpha_min", C.c_float), ("tanfovx", C.c_double), ("tanfovy", C.c_double), ("normals", C.c_void_p),
+                ("valid", C.c_void_p)]
+
+
+class B3gsNormalResizeIO(C.Structure):
+    _fields_ = [("Wsrc", C.c_int32), ("Hsrc", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("src", C.c_void_p),
+                ("src_mask", C.c_void_p), ("normals", C.c_void_p), ("mask", C.c_void_p)]
+
+
 class B3gsKernelTimes(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("sort_ms", C.c_double), ("render_fwd_ms", C.c_double),
                 ("render_bwd_ms", C.c_double), ("preprocess_bwd_ms", C.c_double), ("calls", C.c_int64)]
@@ -299,7 +317,10 @@ EXPORTS = ("b3gs_abi_version", "b3gs_last_error", "b3gs_set_timing", "b3gs_timin
            # added to ABI 18: depth priors (Pearson depth loss, prior resize)
            "b3gs_depth_prior_workspace_bytes", "b3gs_depth_prior_loss_batch", "b3gs_resize_depth_batch",
            # added to ABI 18: per-image exposure compensation (apply, backward, fit, row-sparse Adam)
-           "b3gs_exposure_workspace_bytes", "b3gs_exposure_apply", "b3gs_exposure_backward", "b3gs_exposure_fit", "b3gs_exposure_adam")
+           "b3gs_exposure_workspace_bytes", "b3gs_exposure_apply", "b3gs_exposure_backward", "b3gs_exposure_fit", "b3gs_exposure_adam",
+           # added to ABI 18: normal priors (depth-derived normals, their loss, prior resize)
+           "b3gs_normal_prior_workspace_bytes", "b3gs_normal_prior_loss_batch", "b3gs_depth_normals_batch",
+           "b3gs_resize_normals_batch")
 
 _lib = None
 
@@ -585,6 +606,14 @@ def lib():
     L.b3gs_exposure_fit.restype = C.c_int
     L.b3gs_exposure_adam.argtypes = [I32, V, V, V, V, V, V, V, V, C.c_double, C.c_double, C.c_double, V, V]
     L.b3gs_exposure_adam.restype = C.c_int
+    L.b3gs_normal_prior_workspace_bytes.argtypes = [I32, I32]
+    L.b3gs_normal_prior_workspace_bytes.restype = C.c_size_t
+    L.b3gs_normal_prior_loss_batch.argtypes = [I32, C.POINTER(B3gsNormalPriorIO), V]
+    L.b3gs_normal_prior_loss_batch.restype = C.c_int
+    L.b3gs_depth_normals_batch.argtypes = [I32, C.POINTER(B3gsDepthNormalsIO), V]
+    L.b3gs_depth_normals_batch.restype = C.c_int
+    L.b3gs_resize_normals_batch.argtypes = [I32, C.POINTER(B3gsNormalResizeIO), V]
+    L.b3gs_resize_normals_batch.restype = C.c_int
     L.b3gs_pose_gradient_workspace_bytes.argtypes = [I32, I32]
     L.b3gs_pose_gradient_workspace_bytes.restype = C.c_size_t
     L.b3gs_pose_gradient.argtypes = [I32, I32, I32, V, V, V, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

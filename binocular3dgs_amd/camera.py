@@ -107,16 +107,20 @@ class Camera:
 
     def __init__(self, R, T, FoVx, FoVy, width, height, image=None, gt_alpha_mask=None, uid=0,
                  trans=np.array([0.0, 0.0, 0.0]), scale=1.0, device="cpu", *, prepared=False, image_name=None,
-                 colmap_id=None, bg_mask=None, depth_prior=None, depth_prior_mask=None):
+                 colmap_id=None, bg_mask=None, depth_prior=None, depth_prior_mask=None, normal_prior=None,
+                 normal_prior_mask=None):
         """`prepared=True`: `image` / `gt_alpha_mask` are final already (ground_truth.prepare_ground_truth: clamped and
         multiplied by the mask on the device) and are attached as they are.  `bg_mask`: the DTU background mask
         (train.py:110-120) of this view, computed once.  `depth_prior` / `depth_prior_mask`: a depth (or inverse-depth)
-        prior of this view at the training size, float32 [1,H,W], and its validity, uint8 [1,H,W] (depth_prior.load_priors)."""
+        prior of this view at the training size, float32 [1,H,W], and its validity, uint8 [1,H,W] (depth_prior.load_priors).
+        `normal_prior` / `normal_prior_mask`: unit normals in the camera frame (x right, y down, z forward), float32 [3,H,W], and
+        their validity, uint8 [1,H,W] (normal_prior.load_normal_priors)."""
         self.uid = uid
         self.colmap_id = colmap_id
         self.image_name = image_name
         self.bg_mask = bg_mask
         self.depth_prior, self.depth_prior_mask = depth_prior, depth_prior_mask
+        self.normal_prior, self.normal_prior_mask = normal_prior, normal_prior_mask
         self.R = np.asarray(R, dtype=np.float64)
         self.T = np.asarray(T, dtype=np.float64)
         self.FoVx = float(FoVx)
@@ -186,6 +190,7 @@ class Camera:
         cam.original_image = None if self.original_image is None else self._ones_image()
         cam.gt_alpha_mask = None
         cam.depth_prior = cam.depth_prior_mask = None
+        cam.normal_prior = cam.normal_prior_mask = None
         # All three matrices in closed form on the HOST, one upload: with the matrices in row-vector form only row 3 moves,
         #   wvt'[3,0] = wvt[3,0] - t,   full'[3,:] = wvt'[3,:] @ proj,   centre' = centre + t * wvt[:3,0]  (the camera x axis)
         # (round 3 cloned the view matrix, patched it and re-ran bmm + inverse on the device: ~25 tiny kernels, 54 us of

@@ -95,5 +95,6 @@ void bind_poisson(pybind11::module_& m);
 void bind_mcmc(pybind11::module_& m);
 void bind_depthprior(pybind11::module_& m);
 void bind_exposure(pybind11::module_& m);
+void bind_normalprior(pybind11::module_& m);
 
 }  // namespace b3

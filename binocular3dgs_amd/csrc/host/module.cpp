@@ -73,4 +73,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   b3::bind_mcmc(m);
   b3::bind_depthprior(m);
   b3::bind_exposure(m);
+  b3::bind_normalprior(m);
 }

@@ -271,19 +271,36 @@ def depth_pearson(model, cameras: Sequence, bg: torch.Tensor, priors_dir: str, m
     return [float(x) for x in torch.stack(rhos).cpu()] if rhos else []
 
 
+def normal_cos(model, cameras: Sequence, bg: torch.Tensor, priors_dir: str, frame: str = "opencv", alpha_min: float = 0.5) -> List[float]:
+    """Per camera the mean n.t over the valid pixels between the normals of its rendered depth map and
+    <priors_dir>/<image_name>.npy | .png (normal_prior.load_normal_priors: resized to the camera's size, `frame` converted to
+    the camera frame); a view without a valid pixel scores 0.  One host read, behind the loop."""
+    from .normal_prior import load_normal_priors, normal_prior_loss
+    from .render import PipelineParams, render
+    priors = load_normal_priors(priors_dir, cameras, frame=frame, device=bg.device)
+    dots = []
+    with torch.no_grad():
+        for k, (cam, (target, mask)) in enumerate(zip(cameras, priors)):
+            pkg = render(cam, model, PipelineParams(), bg)
+            _, parts = normal_prior_loss(pkg["rendered_depth"], pkg["rendered_alpha"], target, mask, cam, alpha_min=alpha_min,
+                                         return_parts=True)
+            dots.append(parts[4])
+    return [float(x) for x in torch.stack(dots).cpu()] if dots else []
+
+
 # ---- results.json / per_view.json (metrics.py:105-122) ----------------------------------------------------------------
 def write_results(model_path: str, method: str, per_view: Sequence[dict], names: Sequence[str], aligned: Optional[Sequence[dict]] = None,
                   twists=None, exposure: Optional[Sequence[dict]] = None) -> dict:
     """Writes <model_path>/results.json {method: {"SSIM", "PSNR"}} and per_view.json {method: {"SSIM": {name: v}, "PSNR":
     {name: v}}} in the reference's layout (json.dump, indent=True); the "LPIPS" key is written in both files, as
-    metrics.py:112-117 does, when EVERY per-view entry carries it, and left out otherwise; so is "DepthPearson" (depth_pearson).  Means are fp32, as
+    metrics.py:112-117 does, when EVERY per-view entry carries it, and left out otherwise; so are "DepthPearson" (depth_pearson) and "NormalCos" (normal_cos).  Means are fp32, as
     torch.tensor(values).mean() is there.  `aligned` (the per-view metrics after pose alignment) adds the same keys with the
     suffix _aligned behind them, `twists` ([n,6]) adds per_view.json's "twist": {name: [omega, t]}; without them the files are
     what they were.  `exposure` (the per-view metrics after evaluate_views(fit_exposure=True)) adds the keys with the suffix
     _exposure in the same way and per_view.json's "exposure": {name: 3x4}.  Returns the two dicts."""
     if len(per_view) != len(names) or any(x is not None and len(x) != len(names) for x in (aligned, exposure)):
         raise ValueError("one name per view")
-    keys = ("SSIM", "PSNR") + tuple(k for k in ("LPIPS", "DepthPearson") if per_view and all(k in v for v in per_view))
+    keys = ("SSIM", "PSNR") + tuple(k for k in ("LPIPS", "DepthPearson", "NormalCos") if per_view and all(k in v for v in per_view))
     vals = {k: torch.tensor([float(v[k]) for v in per_view]) for k in keys}
     if aligned is not None:
         vals.update({k + "_aligned": torch.tensor([float(v[k]) for v in aligned]) for k in keys if all(k in v for v in aligned)})
@@ -306,7 +323,8 @@ def write_results(model_path: str, method: str, per_view: Sequence[dict], names:
 # ---- command line: metrics.py over the test cameras of a trained model ------------------------------------------------
 def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1, mode: str = "png", lpips_weights=None,
         masks=None, align_poses: int = 0, align_scales: Sequence[int] = (4, 2, 1), depth_priors: Optional[str] = None,
-        depth_prior_mode: Optional[str] = None, fit_exposure: bool = False) -> dict:
+        depth_prior_mode: Optional[str] = None, fit_exposure: bool = False, normal_priors: Optional[str] = None,
+        normal_prior_frame: Optional[str] = None) -> dict:
     """Loads <model_path>/point_cloud/iteration_<it> and the dataset's test cameras (cfg_args gives the defaults, as in
     spiral.py), evaluates them, prints the means in metrics.py:107-109's format and writes results.json / per_view.json under
     method ours_<it>.  `masks`: DTU IDR object masks per test camera (the command line does not read them).
@@ -314,6 +332,8 @@ def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1,
     and evaluated again; the result gains "aligned" (evaluate_views of the refined cameras) and "twists".
     depth_priors = DIR: "DepthPearson", the mean rho_image against <DIR>/<image_name>.npy of the test views (depth_pearson;
     depth_prior_mode defaults to the run's own in cfg_args), in results.json and per view in per_view.json.
+    normal_priors = DIR: "NormalCos", the mean over the test views of the per-view mean n.t over the valid pixels (normal_cos;
+    normal_prior_frame and alpha_min default to the run's own in cfg_args), in results.json and per view in per_view.json.
     fit_exposure: the views are scored a second time after the best affine colour map onto their ground truth (a held-out
     view has no learned exposure); the result gains "exposure" and the files SSIM_exposure / PSNR_exposure / LPIPS_exposure
     and each view's matrix."""
@@ -347,6 +367,13 @@ def run(model_path: str, source_path: Optional[str] = None, iteration: int = -1,
             v["DepthPearson"] = r
         res["DepthPearson"] = float(torch.tensor(rhos).mean())
         print("  DepthPearson: {:>12.7f}".format(res["DepthPearson"]))
+    if normal_priors:
+        dots = normal_cos(model, cams, bg, normal_priors, normal_prior_frame or cfg.get("normal_prior_frame", "opencv") or "opencv",
+                          float(cfg.get("normal_prior_alpha_min", 0.5) or 0.5))
+        for v, r in zip(res["per_view"], dots):
+            v["NormalCos"] = r
+        res["NormalCos"] = float(torch.tensor(dots).mean())
+        print("  NormalCos: {:>12.7f}".format(res["NormalCos"]))
     print("")
     names = ["{0:05d}.png".format(i) for i in range(len(cams))]      # render.py:34: the file names metrics.py lists
     fit = None
@@ -390,6 +417,9 @@ def main(argv=None) -> int:
     p.add_argument("--depth_priors", default=None, metavar="DIR",
                    help="<image_name>.npy priors of the test views: adds DepthPearson (mean rho_image) to results.json / per_view.json")
     p.add_argument("--depth_prior_mode", choices=("depth", "disparity"), default=None, help="default: the training run's")
+    p.add_argument("--normal_priors", default=None, metavar="DIR",
+                   help="<image_name>.npy | .png normal priors of the test views: adds NormalCos (mean n.t) to results.json / per_view.json")
+    p.add_argument("--normal_prior_frame", choices=("opencv", "opengl", "world"), default=None, help="default: the training run's")
     p.add_argument("--fit_exposure", action="store_true",
                    help="score every view again after the best 3x4 affine colour map onto its ground truth: SSIM_exposure / "
                         "PSNR_exposure / LPIPS_exposure in results.json, each view's matrix in per_view.json")
@@ -406,7 +436,8 @@ def main(argv=None) -> int:
         from .lpips import load_weights
         w = load_weights(a.lpips_vgg, a.lpips_lin)
     run(a.model_path, a.source_path, a.iteration, a.mode, w, align_poses=a.align_poses, align_scales=a.align_scales,
-        depth_priors=a.depth_priors, depth_prior_mode=a.depth_prior_mode, fit_exposure=a.fit_exposure)
+        depth_priors=a.depth_priors, depth_prior_mode=a.depth_prior_mode, fit_exposure=a.fit_exposure,
+        normal_priors=a.normal_priors, normal_prior_frame=a.normal_prior_frame)
     return 0
 
 

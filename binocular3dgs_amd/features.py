@@ -31,7 +31,8 @@ python -m binocular3dgs_amd.features -m MODEL_PATH [-s SOURCE] [--iteration N] [
     render  --features F.npy --views test|all --out DIR [--channels a b c]
                                                                   feature_%05d.npy [C,H,W] and feature_%05d.png: three
                                                                   channels, min-max scaled over the view
-    normals --views test|all --out DIR                            normal_%05d.png of (n + 1) / 2
+    normals --views test|all --out DIR [--source depth]           normal_%05d.png of (n + 1) / 2 (--source depth: depth_normal_%05d.png,
+                                                                  the normals of the rendered depth map, normal_prior.depth_normals)
     select  --features F.npy --view NAME --pixel X Y --threshold T --model_out NEW
                                                                   the Gaussians whose feature is similar to the one rendered
                                                                   at the pixel, as NEW/point_cloud/iteration_<n>/point_cloud.ply
@@ -322,9 +323,30 @@ def run_render(model, cams, features_path: str, out: str, channels=None) -> dict
     return {"rendered": len(cams), "C": C, "channels": ch, "out": out}
 
 
-def run_normals(model, cams, out: str) -> dict:
+def depth_normal_maps(model, cameras: Sequence, *, alpha_min: float = 0.5, background=None):
+    """Yields (camera index, normals float32 [3,H,W], valid bool [H,W]): the normal of every camera's rendered depth map
+    (normal_prior.depth_normals: central differences of the back-projected points), camera frame, 0 where not valid."""
+    from .normal_prior import depth_normals
+    from .render import PipelineParams, render
+    bg = torch.zeros(3, device=model.get_xyz.device) if background is None else background
+    with torch.no_grad():
+        for i, cam in enumerate(cameras):
+            pkg = render(cam, model, PipelineParams(), bg)
+            n, valid = depth_normals(pkg["rendered_depth"], pkg["rendered_alpha"], cam, alpha_min=alpha_min)
+            yield i, n, valid[0] != 0
+
+
+def run_normals(model, cams, out: str, source: str = "gaussians", alpha_min: float = 0.5) -> dict:
+    """source "gaussians": normal_%05d.png of the blended shortest axes; "depth": depth_normal_%05d.png of the depth-derived
+    normals, next to them.  Both as (n + 1) / 2, black where not valid."""
     from . import frames
     os.makedirs(out, exist_ok=True)
+    if source == "depth":
+        for i, n, valid in depth_normal_maps(model, cams, alpha_min=alpha_min):
+            pic = torch.where(valid.unsqueeze(0), (n + 1.0) * 0.5, torch.zeros_like(n))
+            frames.write_png(os.path.join(out, "depth_normal_%05d.png" % i),
+                             (pic * 255.0 + 0.5).clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
+        return {"rendered": len(cams), "out": out, "source": source}
     for i, n, valid in render_normals(model, cams):
         pic = torch.where(valid.unsqueeze(0), (n + 1.0) * 0.5, torch.zeros_like(n))
         frames.write_png(os.path.join(out, "normal_%05d.png" % i), (pic * 255.0 + 0.5).clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
@@ -369,6 +391,9 @@ def main(argv=None) -> int:
     s = sub.add_parser("normals")
     s.add_argument("--views", choices=("test", "all"), default="test")
     s.add_argument("--out", required=True, metavar="DIR")
+    s.add_argument("--source", choices=("gaussians", "depth"), default="gaussians",
+                   help='"depth": the normals of the rendered depth map (depth_normal_%%05d.png) in place of the Gaussians\' axes')
+    s.add_argument("--alpha_min", type=float, default=0.5, help="--source depth: pixels below this alpha carry no normal")
     s = sub.add_parser("select")
     s.add_argument("--features", required=True, metavar="F.npy")
     s.add_argument("--view", required=True, metavar="NAME")
@@ -383,7 +408,7 @@ def main(argv=None) -> int:
     elif a.command == "render":
         res = run_render(model, cams[a.views], a.features, a.out, a.channels)
     elif a.command == "normals":
-        res = run_normals(model, cams[a.views], a.out)
+        res = run_normals(model, cams[a.views], a.out, a.source, a.alpha_min)
     else:
         res = run_select(model, cams["all"], a.features, a.view, a.pixel, a.threshold, a.model_out, it, a.model_path)
     print(json.dumps(res))

@@ -12,18 +12,20 @@ What a captured graph fixes, and where each per-iteration value therefore lives
     the background colour                    three floats of a static block (refreshed when the caller hands in another tensor)
     the depth prior, its validity, the       copied into static buffers next to the mask; the patch offsets: two int32 words
     patch offsets (depth_prior.PriorTerm)    (PriorTerm.offset_buffer) the kernels read, one pinned upload per draw
+    the normal prior and its validity        copied into static buffers in the same way (normal_prior.NormalTerm draws nothing)
     the learning rates                       six floats of the same block (B3gsAdamSegment::lr_dev), one pinned upload
     the exposure row and its learning rate   two words of exposure.ExposureTerm's own block (the table, the moments, the step
     (exposure.ExposureTerm)                  counts are static too), one pinned upload; the kernels read the row on the device
 No value is read back inside an iteration.
 
 What cannot live in device memory is a SHAPE of the graph, captured at its first use and kept:
-    (pair?, opacity decay factor of the Adam launch or 0, statistics on?, mask kind[, "prior"][, "exposure"])
+    (pair?, opacity decay factor of the Adam launch or 0, statistics on?, mask kind[, "prior"][, "exposure"][, "normal"])
 -- single view while `it <= shift_cam_start` or `binocular` is off, the (input, shifted) pair with one depth sort afterwards;
 the fifth entry is there while the depth-prior term is active (all training views carry a prior, or none: a mixed set is
 refused) and ABSENT otherwise, so a run without priors has the keys, the events and the launches it always had; a trailing
 "exposure" is there, in the same way, only while the exposure term is active: the replay then applies the drawn view's row to
 the render (and the shifted partner's) in one launch, and runs the row's Adam behind the fused step under the same capacity word;
+a trailing "normal", likewise, only while the normal-prior term is active (all training views carry one, or none);
 the decay switches on once (`it > densify_from_iter`), the statistics switch off once (`it >= densify_until_iter`, only with
 the decay off: with it on, densification runs to the end).  These windows are schedule.TrainerBase.plan, the one place
 that decides them for both trainers; "the replay carries Adam" is its `step and not densify`.  Every kept graph is dropped, and captured
@@ -81,7 +83,7 @@ class FusedBackend:
     """The device side of GraphTrainer: static storage, the step objects, capture and the capacity word."""
 
     def __init__(self, model, views, background, lambda_dssim=0.2, smooth_weight=0.05, binning_capacity=None, depth_prior=None,
-                 exposure=None):
+                 exposure=None, normal_prior=None):
         from . import _lib, checkpoint
         from .camera import CameraPairSlots, _PinnedRing
         from .fused import FusedRasterizer
@@ -133,6 +135,16 @@ class FusedBackend:
         self.exposure_term = exposure
         self.has_exposure = exposure is not None
         self._exposure = False
+        # normal_prior.NormalTerm: static target plane and validity, copied per view like the depth prior; all views or none
+        self.normal_term = normal_prior if (normal_prior is not None and normal_prior.enabled) else None
+        self.has_normal = False
+        if self.normal_term is not None:
+            from .normal_prior import check_prior_set as check_normal_set
+            self.has_normal = check_normal_set(self.views)
+        if self.has_normal:
+            self.normal = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
+            self.normal_mask = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
+        self._normal = False
         self.fused = FusedRasterizer(model, W, H, num_slots=2, want_means2D=False, binning_capacity=binning_capacity)
         self.st = ViewShardedStep(model, [(self.slots.cam, self.slots.shifted, 0.1)], self.bg, optimizer=self.opt,
                                   fused=self.fused, overflow_check_every=0)
@@ -159,6 +171,9 @@ class FusedBackend:
             self.prior_term.upload_offset(d.offset, self.offset_dev.device)
         if "exposure" in d.key[4:]:
             self.exposure_term.stage(d.view, d.it)
+        if "normal" in d.key[4:]:
+            self.normal.copy_(cam.normal_prior, non_blocking=True)
+            self.normal_mask.copy_(cam.normal_prior_mask, non_blocking=True)
         if d.bg is not self._bg_src:
             self.bg.copy_(d.bg, non_blocking=True)
             self._bg_src = d.bg
@@ -171,7 +186,7 @@ class FusedBackend:
 
     def _configure(self, key):
         pair, decay, stats, kind = key[:4]
-        self._prior, self._exposure = "prior" in key[4:], "exposure" in key[4:]
+        self._prior, self._exposure, self._normal = "prior" in key[4:], "exposure" in key[4:], "normal" in key[4:]
         v0, v1 = self._both
         self.st.views = [v0, v1] if pair else [v0]
         v0.mate = 1 if pair else None
@@ -197,6 +212,8 @@ class FusedBackend:
                                      slot=0, unit_grad=True)
         if self._prior:
             total = total + self.prior_term.loss(cam, pkg, offset_dev=self.offset_dev, prior=self.prior, mask=self.prior_mask)
+        if self._normal:      # (the views share one field of view: the first one's serves the static slot)
+            total = total + self.normal_term.loss(self.views[0], pkg, target=self.normal, mask=self.normal_mask)
         self._loss = total.detach()
         return total
 
@@ -289,7 +306,7 @@ class GraphTrainer(TrainerBase):
         self.check_every = int(check_every)
         self.backend = backend if backend is not None else FusedBackend(model, self.views, background, self.lam,
                                                                         self.smooth_weight, binning_capacity, self.depth_prior,
-                                                                        self.exposure)
+                                                                        self.exposure, self.normal_prior)
         self.events = events
         self.captures = 0        # graphs captured so far: a replay does not move it
         self.grown = 0           # capacity events settled
@@ -375,6 +392,8 @@ class GraphTrainer(TrainerBase):
             key, offset = key + ("prior",), self.depth_prior.draw_offset()      # (the term's own generator; kept for a repeat)
         if getattr(b, "has_exposure", False) and self.exposure.active(it):
             key = key + ("exposure",)
+        if getattr(b, "has_normal", False) and self.normal_prior.active(it):
+            key = key + ("normal",)
         self._run(Draw(it, view_index, float(shift) if plan.pair else None, self.background, lr, key, adam, offset))
         self.densified = False
         if not adam:

@@ -35,7 +35,8 @@ class Scene:
     @classmethod
     def from_dataset(cls, source_path: str, model, *, images="images", eval=True, n_views=3, dataset_name="LLFF", suffix=None,
                      resolution=-1, white_background=False, init_points="matcher", model_path=None, shuffle=True,
-                     load_iteration=None, device="cuda", depth_priors=None):
+                     load_iteration=None, device="cuda", depth_priors=None, normal_priors=None,
+                     normal_prior_frame="opencv"):
         """scene/__init__.py:26-84.  `model`: a GaussianModel (filled from the initial points, or from
         <model_path>/point_cloud/iteration_<load_iteration>, -1 = the latest) or None (cameras only)."""
         import json
@@ -69,6 +70,10 @@ class Scene:
             # <depth_priors>/<image_name>.npy of every TRAINING view -> Camera.depth_prior / depth_prior_mask at its size
             from .depth_prior import attach_priors
             attach_priors(depth_priors, scene.getTrainCameras(), device=device)
+        if normal_priors:
+            # <normal_priors>/<image_name>.npy | .png of every TRAINING view -> Camera.normal_prior / normal_prior_mask
+            from .normal_prior import attach_normal_priors
+            attach_normal_priors(normal_priors, scene.getTrainCameras(), frame=normal_prior_frame, device=device)
         if model is not None:
             if loaded:
                 model.load_ply(os.path.join(model_path, "point_cloud", "iteration_" + str(loaded), "point_cloud.ply"))

@@ -58,7 +58,7 @@ class TrainerBase:
                  opacity_decay_factor=0.995, lambda_dssim=0.2, densify_from_iter=500, densify_until_iter=15_000,
                  densification_interval=100, densify_grad_threshold=0.0002, min_opacity=0.005, sh_interval=1000,
                  smooth_weight=0.05, before_densify=None, test_cameras=None, test_iterations=(), report_fn=None,
-                 after_report=None, depth_prior=None, exposure=None):
+                 after_report=None, depth_prior=None, exposure=None, normal_prior=None):
         self.model, self.scene, self.pipe, self.background = model, scene, pipe, background
         self.iterations, self.shift_cam_start, self.binocular = iterations, shift_cam_start, binocular
         self.decay, self.lam, self.smooth_weight = opacity_decay_factor, lambda_dssim, smooth_weight
@@ -71,6 +71,9 @@ class TrainerBase:
         self.report_fn, self.reports = report_fn, {}
         # depth_prior.PriorTerm or None: a view that carries a `depth_prior` adds the Pearson depth term to the total
         self.depth_prior = depth_prior
+        # normal_prior.NormalTerm or None: a view that carries a `normal_prior` adds the loss between the normals of its rendered
+        # depth map and the prior (gradients in the rendered depth and alpha); None leaves every call and launch as it was
+        self.normal_prior = normal_prior
         # exposure.ExposureTerm or None: the drawn view's render (and its shifted partner's) goes through the view's learned
         # 3x4 colour transform before the loss; None leaves every call, event and launch as it was
         self.exposure = exposure
@@ -177,6 +180,8 @@ class IterationSchedule(TrainerBase):
         total = self._add_loss_terms(recon + stereo + coverage)
         if self.depth_prior is not None:
             total = self.depth_prior.add(total, it, cam, first)
+        if self.normal_prior is not None:
+            total = self.normal_prior.add(total, it, cam, first)
         total.backward()
         self.densified = False
         with torch.no_grad():

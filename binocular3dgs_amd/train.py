@@ -14,6 +14,10 @@ The reference's train.py: a COLMAP / Blender dataset folder in, a trained model 
     --depth_priors DIR     <image_name>.npy depth (or inverse-depth) priors of the training views: the Pearson depth loss of
                            depth_prior.py (both --step modes; --depth_prior_mode depth|disparity, --depth_prior_weight, --depth_prior_local with
                            --depth_prior_patch, --depth_prior_from / --depth_prior_until, --depth_prior_alpha_min)
+    --normal_priors DIR    <image_name>.npy | .png normal priors of the training views (any monocular normal network): the loss of
+                           normal_prior.py between the normals of the rendered depth map and the prior (both --step modes, both
+                           --densify strategies; --normal_prior_frame opencv|opengl|world, --normal_prior_cos, --normal_prior_l1,
+                           --normal_prior_from / --normal_prior_until, --normal_prior_alpha_min)
     --exposure             a learned 3x4 affine colour transform per training image (exposure.ExposureTerm: upstream 3DGS's
                            exposure compensation), applied to the render before the loss; --exposure_lr_init / --exposure_lr_final,
                            --exposure_from IT; exposure.json next to every saved point cloud, chkpnt<n>.exposure.pth next to
@@ -104,6 +108,17 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--depth_prior_from", type=int, default=0)
     p.add_argument("--depth_prior_until", type=int, default=None)
     p.add_argument("--depth_prior_alpha_min", type=float, default=0.0, help="pixels with rendered alpha below this are not used")
+    p.add_argument("--normal_priors", default=None, help="folder of <image_name>.npy (float32 / float64 [H,W,3] or [3,H,W], any size) or "
+                                                         "<image_name>.png (8-bit RGB, n = 2 c / 255 - 1) normal priors for the "
+                                                         "training views; <image_name>_mask.png optional")
+    p.add_argument("--normal_prior_frame", choices=("opencv", "opengl", "world"), default="opencv",
+                   help='the frame the files hold: "opencv" x right, y down, z forward; "opengl" x right, y up, z backward; "world"')
+    p.add_argument("--normal_prior_cos", type=float, default=0.0, help="weight of the mean of 1 - n.t")
+    p.add_argument("--normal_prior_l1", type=float, default=0.0, help="weight of the mean of |n - t|_1")
+    p.add_argument("--normal_prior_from", type=int, default=0)
+    p.add_argument("--normal_prior_until", type=int, default=None)
+    p.add_argument("--normal_prior_alpha_min", type=float, default=0.5,
+                   help="pixels with rendered alpha below this (or next to one) carry no normal; > 0")
     p.add_argument("--exposure", action="store_true", help="learn a 3x4 affine colour transform per training image")
     p.add_argument("--exposure_lr_init", type=float, default=0.01)
     p.add_argument("--exposure_lr_final", type=float, default=0.001)
@@ -124,6 +139,11 @@ def check_args(args) -> None:
         raise ValueError("--depth_prior_weight / --depth_prior_local need --depth_priors DIR, the folder of the priors")
     if wl != 0.0 and not 8 <= getattr(args, "depth_prior_patch", 64) <= 256:
         raise ValueError("--depth_prior_local needs --depth_prior_patch in 8 .. 256")
+    nc, nl = getattr(args, "normal_prior_cos", 0.0) or 0.0, getattr(args, "normal_prior_l1", 0.0) or 0.0
+    if (nc != 0.0 or nl != 0.0) and not getattr(args, "normal_priors", None):
+        raise ValueError("--normal_prior_cos / --normal_prior_l1 need --normal_priors DIR, the folder of the priors")
+    if not getattr(args, "normal_prior_alpha_min", 0.5) > 0.0:
+        raise ValueError("--normal_prior_alpha_min is > 0 (the normal comes from depth / alpha)")
     if getattr(args, "exposure", False):
         if not (getattr(args, "exposure_lr_init", 0.01) > 0.0 and getattr(args, "exposure_lr_final", 0.001) > 0.0):
             raise ValueError("--exposure_lr_init and --exposure_lr_final are > 0 (the schedule is log-linear)")
@@ -173,7 +193,9 @@ def run(args) -> dict:
     scene = Scene.from_dataset(args.source_path, model, images=args.images, eval=args.eval, n_views=args.n_views,
                                dataset_name=args.dataset_name, suffix=args.suffix, resolution=args.resolution,
                                white_background=args.white_background, init_points=args.init_points,
-                               model_path=args.model_path, device=dev, depth_priors=getattr(args, "depth_priors", None))
+                               model_path=args.model_path, device=dev, depth_priors=getattr(args, "depth_priors", None),
+                               normal_priors=getattr(args, "normal_priors", None),
+                               normal_prior_frame=getattr(args, "normal_prior_frame", "opencv"))
     model.training_setup(args)
     first_iter = 0
     if args.start_checkpoint:
@@ -214,6 +236,10 @@ def run(args) -> dict:
         kw["depth_prior"] = PriorTerm(mode=args.depth_prior_mode, weight=args.depth_prior_weight, local=args.depth_prior_local,
                                       patch=args.depth_prior_patch, from_iter=args.depth_prior_from, until_iter=args.depth_prior_until,
                                       alpha_min=args.depth_prior_alpha_min, seed=args.seed)
+    if getattr(args, "normal_priors", None):
+        from .normal_prior import NormalTerm
+        kw["normal_prior"] = NormalTerm(cos=args.normal_prior_cos, l1=args.normal_prior_l1, from_iter=args.normal_prior_from,
+                                        until_iter=args.normal_prior_until, alpha_min=args.normal_prior_alpha_min)
     if exposure is not None:
         kw["exposure"] = exposure
     if getattr(args, "step", "schedule") == "graph":

@@ -1795,6 +1795,89 @@ int b3gs_exposure_adam(int32_t V, float* table, float* exp_avg, float* exp_avg_s
                        const int32_t* row_dev, const double* grad, const float* lr_dev, double beta1, double beta2, double eps,
                        const int32_t* skip_if_nonzero, b3gs_stream_t stream);
 
+/* ---- normal priors: depth-derived normals and their loss (added to ABI 18; csrc/normalprior.hip,
+ * binocular3dgs_amd/normal_prior.py) -------------------------------------------------------------
+ * Four entry points ADDED to ABI 18: no existing declaration, struct or meaning changes, so the number stays.
+ * tests/normal_prior_ref.py restates every rule below in numpy float64.
+ *
+ * All arithmetic is fp64, only + - * / sqrt (and |.|, which is exact), every statement one rounded operation in the order
+ * written, no fma.  Inputs are float32 planes; every output plane is rounded to float32 once.
+ * 1. The depth-derived normal of pixel (x, y), axes x right, y down, z forward, centred pinhole:
+ *      usable   u(x, y) iff alpha >= alpha_min (compared in float32; alpha_min > 0)
+ *      z        = depth / alpha                      (the render is not normalised)
+ *      ray      rx = ((2 (x + 0.5)) / W - 1) tanfovx,  ry = ((2 (y + 0.5)) / H - 1) tanfovy,  rz = 1
+ *      point    p = (z rx, z ry, z)
+ *      tangents tx = p(x + 1, y) - p(x - 1, y),  ty = p(x, y + 1) - p(x, y - 1)      (1 <= x <= W - 2, 1 <= y <= H - 2)
+ *      c        = cross(ty, tx) = (ty_y tx_z - ty_z tx_y,  ty_z tx_x - ty_x tx_z,  ty_x tx_y - ty_y tx_x)
+ *                 (a fronto-parallel surface: c points at the camera, c_z < 0)
+ *      cc = (c_x c_x + c_y c_y) + c_z c_z,  s = sqrt(cc),  n = c / s
+ *      valid    v(x, y) iff the pixel is interior, u holds at it and at its four axis neighbours, cc > 0 and cc < +inf, and the
+ *               target's mask byte is non-zero (no mask: every byte counts as 1).  Elsewhere n = 0 and valid = 0.
+ * 2. b3gs_normal_prior_loss_batch: against a unit target plane t (float32 [3, H, W], camera frame), with N = #valid
+ *      per valid pixel   dot = (n_x t_x + n_y t_y) + n_z t_z,  a = 1 - dot,  b = (|n_x - t_x| + |n_y - t_y|) + |n_z - t_z|
+ *      block sums        block k holds pixels 256 k .. 256 k + 255 (row-major); its three sums (count, a, b; 0 for a pixel that
+ *                        is not valid) are the TREE of section "depth priors"; the image sums are the FOLD of the block sums.
+ *      parts             cos_term = S_a / N, l1_term = S_b / N, L = w_cos cos_term + w_l1 l1_term;
+ *                        parts = [L, cos_term, l1_term, N, 1 - cos_term (the mean n.t), 0]; N == 0: all six are 0.
+ *      adjoint of n      h_k = w_l1 sgn(n_k - t_k) - w_cos t_k  (sgn(0) = 0); UNSCALED: 1 / N enters last
+ *      through n = c/s   d = (n_x h_x + n_y h_y) + n_z h_z,  e_k = (h_k - n_k d) / s
+ *      tangent adjoints  g_ty = cross(tx, e),  g_tx = cross(e, ty)  (the component order of c above); 0 where not valid
+ *      gather, pixel q   g_p(q) = ((g_tx(x - 1, y) - g_tx(x + 1, y)) + g_ty(x, y - 1)) - g_ty(x, y + 1) per component, a term whose
+ *                        centre lies outside the image entering as 0
+ *      g_z = ((g_p_x rx + g_p_y ry) + g_p_z) (1 / N)           (1 / N read from device memory; 0 when N == 0)
+ *      dL_ddepth = (float)(g_z / alpha),  dL_dalpha = (float)((0 - g_z z) / alpha);  both 0 where u(q) does not hold
+ *    Two launches for all views of the call: (1) thread = pixel: n, validity, the block sums, the tangent adjoints into the
+ *    workspace (48 bytes per pixel), the FOLD by the last workgroup of a view to arrive, which also writes parts and 1 / N and
+ *    resets the arrival counter; (2) the gather.  No host read, no allocation, no floating-point atomic.  `normals` / `valid`:
+ *    NULL, or planes that receive n and v.  `mask` may be NULL.  `workspace`: b3gs_normal_prior_workspace_bytes(W, H) bytes (0
+ *    for sizes outside 1 <= W, H, W H <= 2^24), 256-byte aligned, ZERO before its first use; a call leaves it ready for the
+ *    next.  Its float64 words: [0] the counter, [8] 1 / N, [32 + 3 k ..] the sums of block k.
+ * 3. b3gs_depth_normals_batch: rule 1 alone, one launch.
+ * 4. b3gs_resize_normals_batch: a prior [3, Hsrc, Wsrc] of any size -> the training size.  Taps, weights and the float32 fma
+ *    chain per component are those of b3gs_resize_depth_batch.  A source pixel is good iff its three components are finite (and,
+ *    with src_mask, its byte != 0).  In fp64 from the three float32 results: l = (v_x v_x + v_y v_y) + v_z v_z; the output pixel
+ *    is valid iff every tap of non-zero weight is good and l >= 1/4: then n = (float)(v / sqrt(l)), mask = 1; else n = 0, mask = 0.
+ * Every entry point checks its arguments before the first HIP call: B3GS_ERR_ARG with a message for NULL pointers, n_views
+ * outside 1 .. 8, bad sizes, alpha_min <= 0 or NaN, NaN weights, tanfov <= 0 or NaN, a misaligned workspace. */
+#define B3GS_NORMAL_PRIOR_MAX_VIEWS 8
+typedef struct B3gsNormalPriorIO {
+  int32_t W, H;
+  const float* depth;          /* [H, W] rendered depth */
+  const float* alpha;          /* [H, W] rendered alpha */
+  const float* target;         /* [3, H, W] unit normals, camera frame */
+  const uint8_t* mask;         /* NULL, or [H, W] validity of the target */
+  float alpha_min;             /* > 0 */
+  double tanfovx, tanfovy;     /* > 0 */
+  double w_cos, w_l1;
+  float* dL_ddepth;            /* [H, W], every word written */
+  float* dL_dalpha;            /* [H, W], every word written */
+  float* normals;              /* NULL, or [3, H, W] */
+  uint8_t* valid;              /* NULL, or [H, W] */
+  double* parts;               /* [6] on the device */
+  void* workspace;
+} B3gsNormalPriorIO;
+typedef struct B3gsDepthNormalsIO {
+  int32_t W, H;
+  const float* depth;          /* [H, W] */
+  const float* alpha;          /* [H, W] */
+  const uint8_t* mask;         /* NULL, or [H, W] */
+  float alpha_min;
+  double tanfovx, tanfovy;
+  float* normals;              /* [3, H, W] */
+  uint8_t* valid;              /* [H, W] */
+} B3gsDepthNormalsIO;
+typedef struct B3gsNormalResizeIO {
+  int32_t Wsrc, Hsrc, W, H;
+  const float* src;            /* [3, Hsrc, Wsrc] */
+  const uint8_t* src_mask;     /* NULL, or [Hsrc, Wsrc] */
+  float* normals;              /* [3, H, W] */
+  uint8_t* mask;               /* [H, W] */
+} B3gsNormalResizeIO;
+size_t b3gs_normal_prior_workspace_bytes(int32_t W, int32_t H);
+int b3gs_normal_prior_loss_batch(int32_t n_views, const B3gsNormalPriorIO* io, b3gs_stream_t stream);
+int b3gs_depth_normals_batch(int32_t n_views, const B3gsDepthNormalsIO* io, b3gs_stream_t stream);
+int b3gs_resize_normals_batch(int32_t n_views, const B3gsNormalResizeIO* io, b3gs_stream_t stream);
+
 /* ---- scale initialisation -------------------------------------------------------------
  * mean_dist2[i] = mean squared distance from point i to its 3 nearest OTHER points: the distCUDA2 of the
  * reference's simple-knn extension (scene/gaussian_model.py:134: scales = log(sqrt(max(dist2, 1e-7)))).
